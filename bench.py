@@ -25,6 +25,12 @@ the reference-equivalent rate (the reference computes every one of those node
 updates).  computed_updates_* report the updates actually computed per pattern
 (cherry-table nodes are lookups, SURVEY 8(d) "effective"), and roofline.executed the
 fp64 work the kernels really issue (plk_traversal_work, counted from the program).
+
+A plain run sets up, warms up, times the K steps and prints the line.  --dump-outputs DIR
+also writes what the last timed step returned (lnl.npy, block_sums.npy).  --full adds the
+secondary measurements, each a run of its own after the timed steps: the oracle's 1-core
+CPU baseline with the GPU-vs-oracle parity figures (`cpu_baseline`) and the config-5
+strong-scaling sub-record (`strong`).
 """
 from __future__ import annotations
 
@@ -61,8 +67,18 @@ def parse():
                          "(e.g. 0,0 rehearses two shards on one GPU; the line is then marked a rehearsal)")
     ap.add_argument("--sim-cpu", default=None, choices=["numpy", "torch"],
                     help="simulate the alignment on the host (default: on the GPU, the same states bitwise)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the secondary measurements of the line: the oracle's "
+                         "1-core CPU baseline with its parity figures (`cpu_baseline`) and the config-5 "
+                         "strong-scaling sub-record (`strong`).  A plain run sets up, warms up, times the "
+                         "steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned to its caller as DIR/<name>.npy (float64): "
+                         "lnl.npy, the log-likelihood, and block_sums.npy, the fixed-order 4096-pattern block "
+                         "sums of this process's patterns.  The inputs are seeded, so equal arguments give "
+                         "equal inputs from run to run")
     ap.add_argument("--no-strong", action="store_true",
-                    help="skip the config-5 strong-scaling sub-record of the default line")
+                    help="with --full: skip the config-5 strong-scaling sub-record")
     ap.add_argument("--strong-steps", type=int, default=40, help="timed steps of the strong sub-record (~0.1 s)")
     ap.add_argument("--strong-patterns", type=int, default=None,
                     help="tests only: patterns of the strong sub-record (default config 5's 2M)")
@@ -84,7 +100,7 @@ def parse():
                     help="A/B experiments only: the config's model with this many Gamma classes")
     ap.add_argument("--cpu-sample", type=int, default=None, help="patterns in the CPU-baseline sample")
     ap.add_argument("--cpu-runs", type=int, default=5, help="timed CPU-baseline traversals per variant (median, after 1 warm-up)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-events", action="store_true", help="A/B: time the steps without per-kernel HIP events")
     ap.add_argument("--event-every", type=int, default=4,
                     help="HIP events bracket the partials launches of every K-th timed step (an event pair costs "
@@ -395,8 +411,8 @@ def measure(args, lay, ctx, config, scaling, patterns=None, classes=None, mode="
     def one_step():
         lnl, _, blocks = ev.step()
         if xchg is None:
-            return lnl  # global: plk_evaluate summed every rank's / device's block sums in global order
-        return xchg.lnl(blocks)
+            return lnl, blocks  # global: plk_evaluate summed every rank's / device's block sums in global order
+        return xchg.lnl(blocks), blocks
 
     if dist is not None and not rehearse:
         # check the in-handle exchange once against torch.distributed's all-gather of the
@@ -405,12 +421,12 @@ def measure(args, lay, ctx, config, scaling, patterns=None, classes=None, mode="
         ref = shard.BlockExchange(dist, ev.n_blocks, device=ctx["coll_dev"]).lnl(blocks0)
         if ref != lnl0:
             raise RuntimeError(f"rank {rank}: in-handle RCCL lnL {lnl0!r} != torch all-gather {ref!r}")
-    lnl = None
+    lnl = blocks = None
     clk = args.clock_json and steps == args.steps   # (the main measurement, not the strong sub-record)
     step_ms = []
     for _ in range(warmup):
         tw = time.perf_counter()
-        lnl = one_step()
+        lnl, blocks = one_step()
         step_ms.append((time.perf_counter() - tw) * 1e3)
     ev.eng.reset_timing()
     # HIP events around the traversal launches and their table builds only (each timed
@@ -432,10 +448,10 @@ def measure(args, lay, ctx, config, scaling, patterns=None, classes=None, mode="
             ev.eng.set_timing(0)
         if clk:
             tw = time.perf_counter()
-            lnl = one_step()
+            lnl, blocks = one_step()
             step_ms.append((time.perf_counter() - tw) * 1e3)
         else:
-            lnl = one_step()
+            lnl, blocks = one_step()
     if dist is not None:
         dist.barrier()
     ev.eng.synchronize()
@@ -462,9 +478,19 @@ def measure(args, lay, ctx, config, scaling, patterns=None, classes=None, mode="
         elapsed = float(e.item())
     units_step = P_job * wl.et.n_internal   # the whole job's node updates per step
     fan = ev.eng.fanout() if lay["kind"] == "multi" else None
-    return {"wl": wl, "ev": ev, "P": P_timed, "P_job": P_job, "lnl": lnl, "elapsed": elapsed, "tm": tm, "fanout": fan,
-            "ev_steps": ev_steps, "k_ev": k_ev, "steps": steps, "units_step": units_step, "t_setup": t_setup,
+    return {"wl": wl, "ev": ev, "P": P_timed, "P_job": P_job, "lnl": lnl, "blocks": blocks, "elapsed": elapsed, "tm": tm,
+            "fanout": fan, "ev_steps": ev_steps, "k_ev": k_ev, "steps": steps, "units_step": units_step, "t_setup": t_setup,
             "value": units_step * steps / elapsed, "ms_step": elapsed * 1e3 / steps}
+
+
+def dump_outputs(directory: str, m: dict) -> None:
+    """--dump-outputs: what the last timed step (the last warm-up step when --steps is 0)
+    returned, one float64 array per file."""
+    if m["blocks"] is None:
+        raise SystemExit("bench.py: --dump-outputs needs at least one step")
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "lnl.npy"), np.array([m["lnl"]], dtype=np.float64))
+    np.save(os.path.join(directory, "block_sums.npy"), np.asarray(m["blocks"], dtype=np.float64))
 
 
 def parallelism(lay, args) -> str:
@@ -579,13 +605,15 @@ def main():
                                     f"path exercised, not an {args.gpus}-GPU measurement")
         if args.mode == "subtree":
             rec["metric"] += " (EFFECTIVE: per-subtree pattern compression)"
-        if world == 1 and lay["kind"] == "single" and not args.no_cpu_baseline:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, m)
+        if args.full and world == 1 and lay["kind"] == "single" and not args.no_cpu_baseline:
             ns = args.cpu_sample or workload.CONFIGS[args.config]["cpu_sample"]
             _, eng_sites, _ = ev.eng.root_loglik(wl.et.root, want_sites=True)
             rec["cpu_baseline"] = cpu_baseline(wl, min(ns, P), args.cpu_runs, eng_sites)
     ev.eng.close()
     del m, ev
-    if not args.no_strong and args.scaling == "weak" and args.config == "gtr_g4_dna_1M_64":
+    if args.full and not args.no_strong and args.scaling == "weak" and args.config == "gtr_g4_dna_1M_64":
         # the strong-scaling curve BASELINE config 5 names, from the same sweep: config 5's 2M
         # patterns split over the same N GPUs, timed the same way (the N = 1 line is all 2M on
         # one GPU), so the driver's N = 1, 2, 4, 8 lines carry both curves

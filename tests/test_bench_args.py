@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 _REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -69,6 +70,28 @@ def test_single_gpu_explicit_device(bench):
     assert bench.single_device(bench.launch_layout(_args())) == 0
     with pytest.raises(SystemExit):
         bench.launch_layout(_args(gpus=1, devices="0,1"))
+
+
+def test_full_and_dump_outputs_are_off_by_default(bench, monkeypatch):
+    """A plain run times its steps and prints the line: the CPU baseline and the strong
+    sub-record need --full, the output files --dump-outputs DIR."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d"
+
+
+def test_dump_outputs_writes_float64_arrays(bench, tmp_path):
+    d = tmp_path / "a" / "b"
+    bench.dump_outputs(str(d), {"lnl": -1.5, "blocks": np.array([-1.0, -0.5])})
+    assert sorted(os.listdir(d)) == ["block_sums.npy", "lnl.npy"]
+    lnl, blocks = np.load(d / "lnl.npy"), np.load(d / "block_sums.npy")
+    assert lnl.dtype == blocks.dtype == np.float64
+    assert lnl.tolist() == [-1.5] and blocks.tolist() == [-1.0, -0.5]
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(d), {"lnl": None, "blocks": None})
 
 
 def test_cli_exits_nonzero_without_gpus(tmp_path):

@@ -47,14 +47,15 @@ def test_cpp_drop_in_nh():
     ("test_likelihood_nh", ()),
 ])
 def test_reference_likelihood_test_runs_unchanged(name, goldens, tmp_path):
-    """The reference's own test program (/root/reference/test/<name>.cpp, compiled unchanged
-    against the Bio++ mirror by the host Makefile in the build container: bin/ref_<name>) runs
-    on the MI355X and passes its own checks (exit status 0: the goldens at its 0.001 / 0.0001
-    tolerances, the SR vs DR derivatives, the NH theta recovery).  The printed -lnL values are
-    also checked here, in the order the program prints them."""
+    """The reference's own test program (the reference's test/<name>.cpp, compiled unchanged
+    against the Bio++ mirror where the reference is present, by `make -C oracle ref` as build()
+    runs it: oracle/_ref/ref_<name>) runs on the MI355X and passes its own checks (exit status
+    0: the goldens at its 0.001 / 0.0001 tolerances, the SR vs DR derivatives, the NH theta
+    recovery).  The printed -lnL values are also checked here, in the order the program
+    prints them."""
     assert plk.device_count() > 0, "no GPU visible"
-    exe = os.path.join(HOST, "bin", "ref_" + name)
-    assert os.path.exists(exe), f"{exe} missing: build it where /root/reference exists (make -C {HOST})"
+    exe = os.path.join(ROOT, "oracle", "_ref", "ref_" + name)
+    assert os.path.exists(exe), f"{exe} missing: build it where the reference is present (make -C oracle ref)"
     r = subprocess.run([exe], capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
     print(r.stdout[-6000:])
     print(r.stderr[-3000:])

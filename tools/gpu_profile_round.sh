@@ -19,8 +19,10 @@ fi
 bash tools/gpu_prof.sh ${P}_cfg3_lnl lg08_g4_protein_200k_256 lnl 5 || exit 1
 bash tools/gpu_prof.sh ${P}_cfg4_lnl yn98_codon_50k_128 lnl 10 || exit 1
 bash tools/gpu_prof.sh ${P}_cfg5_lnl nh_gtr_g4_dna_2M_512 lnl 10 || exit 1
-timeout -k 10 300 python bench.py > gpurun_out/${P}_bench_default.json 2> gpurun_out/${P}_bench_default.err || { tail -5 gpurun_out/${P}_bench_default.err; exit 1; }
-cat gpurun_out/${P}_bench_default.json
+# the default line with its CPU baseline and strong sub-record (--full), under BENCH_LINE_DIR
+D=${BENCH_LINE_DIR:-profiles/_run}; mkdir -p $D
+timeout -k 10 300 python bench.py --full > $D/${P}_bench_default.json 2> $D/${P}_bench_default.err || { tail -5 $D/${P}_bench_default.err; exit 1; }
+cat $D/${P}_bench_default.json
 # row f4: the double-recursive all-branch derivative pass (kernel-trace stats)
 mkdir -p gpurun_out/prof/${P}_cfg2_dr
 ( export TMPDIR=/tmp; cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/gpurun_out/prof/${P}_cfg2_dr/trace -o run -- \
