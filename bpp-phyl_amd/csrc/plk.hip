@@ -882,7 +882,7 @@ int root_finish_c(plk_handle h, double* lnl, double* block_sums);
 
 namespace {
 double* block_target(plk_handle h);
-void launch_cls_blocks(plk_handle h, int guard, int32_t* uflow, bool site);
+int launch_cls_blocks(plk_handle h, int guard, int32_t* uflow, bool site);
 
 // The root reductions of an unscaled handle flag a site likelihood below 2^-255 (or <= 0, or
 // NaN) in mapped host memory (plk_root_underflow); a scaled handle's reductions see rescaled
@@ -2220,6 +2220,12 @@ int update_tree4(plk_handle h, const plk_op* ops, int n_ops) {
       }
     }
     sh.G = std::max(1, std::min(sh.G, 1024 / (64 * sh.nw())));  // (a JIT_G past 1024 threads)
+    // wave tasks (direct codes, one wave per pattern group): no barrier in the loop, every wave
+    // walks its own 64 * PW-pattern tasks (plk_jit.hpp; PLK_TUNE JIT_WT=0 is the super-block
+    // schedule with its barrier per super-block, kept for A/B runs)
+    // (on for one class per workgroup, where the barrier wait was 22 % of a wave's loop; the
+    // every-class-in-the-wave kernel waits 1.8 % there and keeps the super-block schedule)
+    sh.wt = sh.wt_ok() && tune_int("JIT_WT", sh.cls ? 1 : 0, 0, 1) != 0;
     // two patterns per lane halve the P(t) reads per FMA but double the registers:
     // measured slower (cfg2 0.255-0.301 vs 0.241 ms), so opt-in; not with speculation
     // two-stage pipeline, codes / HBM loads 3 ahead (cfg2 0.274 -> 0.259 ms); with every
@@ -2232,12 +2238,15 @@ int update_tree4(plk_handle h, const plk_op* ops, int n_ops) {
     // fires; on cfg5 it fires in almost every super-block (1.27 vs 1.14 ms), so opt-in
     // classes in the wave: next class's P(t) loads overlap this class's FMAs
     sh.ppipe = true;
-    sh.clk = env_is("PLK_DEBUG_CLOCK", '1') ? 1 : env_is("PLK_DEBUG_CLOCK", '2') ? 2 : 0;
+    sh.clk = env_is("PLK_DEBUG_CLOCK", '1') ? 1 : env_is("PLK_DEBUG_CLOCK", '2') ? 2 : env_is("PLK_DEBUG_CLOCK", '3') ? 3 : 0;
     // PLK_JIT_BLOCKS=1: the root fragment forms the block sums (no wave_sums_to_blocks
     // launch).  Measured slower (cfg2 traversal 0.125 -> 0.160 ms): the wave that stores a
     // wave sum must wait for the store and the counter's atomic round trip (~3 us) before
     // its workgroup's next super-block barrier, in every super-block.  Off; the formal
-    // release/acquire form (an L2 write-back per wave) was slower still (round 1)
+    // release/acquire form (an L2 write-back per wave) was slower still (round 1).
+    // (That barrier is what wave tasks take out of the loop -- sh.wt above: a round of the
+    // super-block schedule costs what its slowest wave costs.  The class reduction stays a
+    // launch of its own: its handshake would put the same round trip back into every task.)
     if (sh.lds_bytes() > 160 * 1024 - 64)  // (less the kernel's static LDS word)
       return fail(h, PLK_ERR_UNSUPPORTED, "tree kernel needs %zu B of LDS", sh.lds_bytes());
     if (!h->jit_fn || sh.C != h->jit_shape.C || sh.CW != h->jit_shape.CW ||
@@ -2246,7 +2255,7 @@ int update_tree4(plk_handle h, const plk_op* ops, int n_ops) {
         sh.NT != h->jit_shape.NT || sh.TD != h->jit_shape.TD || sh.scale != h->jit_shape.scale || sh.L != h->jit_shape.L ||
         sh.minw != h->jit_shape.minw || sh.ppipe != h->jit_shape.ppipe || sh.clk != h->jit_shape.clk ||
         sh.cls != h->jit_shape.cls || sh.soa != h->jit_shape.soa || sh.ps1 != h->jit_shape.ps1 || sh.RD != h->jit_shape.RD ||
-        sh.dc != h->jit_shape.dc || sh.dcw != h->jit_shape.dcw) {
+        sh.dc != h->jit_shape.dc || sh.dcw != h->jit_shape.dcw || sh.wt != h->jit_shape.wt) {
       int rc = jit_function(h, jit_tree4_source(h->jit_plan, sh), jit_tree4_name(sh), &h->jit_fn);
       if (rc) return rc;
       h->jit_shape = sh;
@@ -2265,6 +2274,7 @@ int update_tree4(plk_handle h, const plk_op* ops, int n_ops) {
     ja.n_pad = a.n_pad;
     ja.n_patterns = a.n_patterns;
     ja.n_sblocks = (int32_t)((h->n_pad + 64 * sh.G * sh.PW - 1) / (64 * sh.G * sh.PW));  // last may be ragged
+    ja.n_tasks = (int32_t)((h->n_pad + 64 * sh.PW - 1) / (64 * sh.PW));  // (wave tasks; n_pad is whole tiles)
     ja.guard = a.guard;
     ja.sb_ctr = h->d_sbctr;
     ja.dyn = tune_is("JIT_DYN", '0') ? 0 : 1;  // (per launch below)
@@ -2329,7 +2339,9 @@ int update_tree4(plk_handle h, const plk_op* ops, int n_ops) {
     // stamp buffer for every workgroup of every tier's launch (grids below: at most
     // jit_resident workgroups per fragment of a tier)
     size_t need = 0;
-    for (const auto& t : h->prog_tiers) need += (size_t)(h->n_pad / 64) * t.size() * (h->jit_shape.cls ? h->C : 1);
+    // (PLK_DEBUG_CLOCK=3: one record per wave; a ragged last workgroup still has all its waves)
+    const size_t per = h->jit_shape.clk == 3 ? (size_t)(h->n_pad / 64 + 16) * h->jit_shape.nw() : (size_t)(h->n_pad / 64);
+    for (const auto& t : h->prog_tiers) need += per * t.size() * (h->jit_shape.cls ? h->C : 1);
     if (need > h->clk_cap) {
       if (h->h_clk) hipHostFree(h->h_clk);
       h->h_clk = nullptr;
@@ -2370,11 +2382,21 @@ int update_tree4(plk_handle h, const plk_op* ops, int n_ops) {
         // instead of the tier's fragments running one after another with every workgroup
         // staging tables for a few super-blocks (cfg5 0.49 -> 0.42 ms)
         wgs = std::max(1, h->jit_resident / ((int)grid.y * gz));
+        // PLK_TUNE JIT_WGS=<n>: at most n persistent workgroups per (fragment, class), so that a
+        // few thousand patterns walk many tasks per workgroup (the dynamic order in small tests)
+        if (const int cap = tune_int("JIT_WGS", 0, 0, 1 << 20)) wgs = std::min(wgs, cap);
       }
       const unsigned gx = (unsigned)std::min<int64_t>(ja.n_sblocks, wgs);
       // dynamic super-blocks where a workgroup walks several (a tier of 1-2 per workgroup
-      // gains nothing from them and pays the counter's round trips)
-      ja.dyn = (!tune_is("JIT_DYN", '0') && ja.n_sblocks >= 3 * (int64_t)gx) ? 1 : 0;
+      // gains nothing from them and pays the counter's round trips); wave tasks: where a wave
+      // walks at least three
+      const int64_t units = sh.wt ? ja.n_tasks : ja.n_sblocks, walkers = sh.wt ? (int64_t)gx * sh.G : (int64_t)gx;
+      // (wave tasks take tickets only when asked to, JIT_DYN=1: one ticket per 128-pattern task
+      // is 16 x the atomics on the same counter words, and at cfg2's 1 M patterns -- 7 813
+      // tasks per class over 1 024 waves -- the traversal ran 388 us against 83 with the
+      // super-block schedule, profiles/r07/ab_runs.md; the static stride needs none)
+      const bool dyn_on = sh.wt ? tune_is("JIT_DYN", '1') : !tune_is("JIT_DYN", '0');
+      ja.dyn = (dyn_on && units >= 3 * walkers) ? 1 : 0;
       // the launch's counters start at 0; its last workgroup leaves them at 0 (exit ticket)
       ja.exit_ctr = ja.dyn ? h->d_sbctr + (size_t)h->prog_nf * h->C : nullptr;
       h->jit_last_gx = (int)gx;
@@ -2383,12 +2405,12 @@ int update_tree4(plk_handle h, const plk_op* ops, int n_ops) {
       HIPCHK(h, hipModuleLaunchKernel(h->jit_fn, gx, grid.y, (unsigned)gz, 64 * sh.nw() * sh.G, 1, 1,
                                       (unsigned)sh.lds_bytes(),
                                       h->stream, args, nullptr));
-      if (sh.clk) h->clk_n += (size_t)gx * grid.y * gz;
+      if (sh.clk) h->clk_n += (size_t)gx * grid.y * gz * (sh.clk == 3 ? (size_t)sh.nw() * sh.G : 1);
       if (sh.cls && h->prog_root >= 0 && first + (int)t.size() == h->prog_nf) {
         // the classes' root terms meet here: log, site lnL, wave and block sums (the work of
         // reduce_root and wave_sums_to_blocks), inside the traversal's timing
         h->fused_cls_blocks = block_target(h);
-        launch_cls_blocks(h, ja.guard, ja.uflow, false);
+        if (int rc = launch_cls_blocks(h, ja.guard, ja.uflow, false)) return rc;
       }
     } else if (jitm) {
       int base = first;
@@ -3770,7 +3792,7 @@ double* block_target(plk_handle h) { return h->comm ? h->d_blk_local : h->block_
 // The classes' root terms of a one-class-per-workgroup traversal -> site lnL and block sums
 // (cls_blocks_kernel) into h->fused_cls_blocks
 // (site: also the per-pattern lnL -- an evaluation that returns only the lnL skips those stores)
-void launch_cls_blocks(plk_handle h, int guard, int32_t* uflow, bool site) {
+int launch_cls_blocks(plk_handle h, int guard, int32_t* uflow, bool site) {
   const int n_waves = (int)((h->n_patterns + 63) / 64);
   const dim3 g((unsigned)h->n_blocks), b(1024);
   double* sl = site ? h->site_lnl : nullptr;
@@ -3780,9 +3802,11 @@ void launch_cls_blocks(plk_handle h, int guard, int32_t* uflow, bool site) {
                                                         h->fused_cls_blocks, h->n_patterns, n_waves, guard, uflow); break;
     case 2: cls_blocks_kernel<2><<<g, b, 0, h->stream>>>(h->d_cls, h->n_pad, h->weights, sl,
                                                         h->fused_cls_blocks, h->n_patterns, n_waves, guard, uflow); break;
-    default: cls_blocks_kernel<4><<<g, b, 0, h->stream>>>(h->d_cls, h->n_pad, h->weights, sl,
-                                                         h->fused_cls_blocks, h->n_patterns, n_waves, guard, uflow);
+    case 4: cls_blocks_kernel<4><<<g, b, 0, h->stream>>>(h->d_cls, h->n_pad, h->weights, sl,
+                                                        h->fused_cls_blocks, h->n_patterns, n_waves, guard, uflow); break;
+    default: return fail(h, PLK_ERR_ARG, "class block sums: %d rate classes (1, 2 or 4)", h->C);
   }
+  return PLK_OK;
 }
 
 // The fixed-order 4096-pattern block sums of the wave sums; under a communicator also the
@@ -3815,10 +3839,14 @@ int root_launch(plk_handle h, int root, double* site_lnl) {
     } else if (h->fused_cls_blocks) {
       // again: block sums to the communicator's buffer, or the per-pattern lnL asked for
       h->fused_cls_blocks = block_target(h);
-      launch_cls_blocks(h, (h->flags & PLK_FLAG_NONNEG_GUARD) ? 1 : 0,
-                        (h->flags & PLK_FLAG_SCALING) ? nullptr : h->d_uflow, site_lnl != nullptr);
+      if (int rc = launch_cls_blocks(h, (h->flags & PLK_FLAG_NONNEG_GUARD) ? 1 : 0,
+                                     (h->flags & PLK_FLAG_SCALING) ? nullptr : h->d_uflow, site_lnl != nullptr))
+        return rc;
       HIPCHK(h, hipGetLastError());
-      if (h->comm) flag_slot_kernel<<<1, 1, 0, h->stream>>>(h->d_uflow, h->d_blk_local + h->comm_stride - 1);
+      if (h->comm) {
+        flag_slot_kernel<<<1, 1, 0, h->stream>>>(h->d_uflow, h->d_blk_local + h->comm_stride - 1);
+        HIPCHK(h, hipGetLastError());
+      }
     } else {
       int rc = launch_block_sums(h);
       if (rc) return rc;
@@ -3851,6 +3879,27 @@ int root_launch(plk_handle h, int root, double* site_lnl) {
 // [1] / [2] the slowest / fastest workgroup's, [3] first start to last end in us, [4] workgroups
 void clock_summary(plk_handle h) {
   if (!h->clk_n) return;
+  if (h->jit_shape.clk == 3) {
+    // PLK_DEBUG_CLOCK=3, one record per wave (plk_jit.hpp): [0] the barrier-wait share of loop
+    // time, mean over the waves that ran (the first round's barrier, which also waits for the
+    // table staging, left out of both), [1] the worst wave's share, [2] / [3] mean / longest
+    // loop in shader-clock ticks, [4] waves that ran
+    double ss = 0.0, worst = 0.0, sl = 0.0, ml = 0.0, n = 0.0;
+    for (size_t i = 0; i < h->clk_n; ++i) {
+      const volatile unsigned long long* q = h->h_clk + 4 * i;
+      if (!q[3] || q[0] <= q[2]) continue;
+      const double loop = (double)(q[0] - q[2]), share = (double)q[1] / loop;
+      ss += share;
+      worst = std::max(worst, share);
+      sl += loop;
+      ml = std::max(ml, loop);
+      n += 1.0;
+    }
+    const double rec[5] = {n > 0 ? ss / n : 0.0, worst, n > 0 ? sl / n : 0.0, ml, n};
+    h->clk_rec.insert(h->clk_rec.end(), rec, rec + 5);
+    h->clk_n = 0;
+    return;
+  }
   double sc = 0.0, sw = 0.0, lo = 1e30, hi = 0.0;
   unsigned long long w0 = ~0ull, w1 = 0;
   for (size_t i = 0; i < h->clk_n; ++i) {

@@ -400,7 +400,13 @@ struct JArgs {
   unsigned* exit_ctr;
   int32_t* uflow;  // unscaled handles: set to 1 when a site likelihood is < 2^-255 (or null)
   double* cls_sum;  // JitShape::cls: every class's root term per pattern, [C][n_pad] (class_sums_to_blocks)
+  // JitShape::wt: wave tasks of 64 * PW patterns, ceil(n_pad / (64 * PW)).  Last, and declared
+  // only by the wave-task programs' prelude (kJitArgsTail / kJitArgsTailWt): the other
+  // programs' JArgs ends at cls_sum and their sources stay as they were
+  int32_t n_tasks;
 };
+static const char* kJitArgsTail = "[C][n_pad]\n};";
+static const char* kJitArgsTailWt = "[C][n_pad]\n  i32 n_tasks;  // wave tasks (64 * PW_ patterns each)\n};";
 
 struct JitShape {
   int C = 1;        // rate classes
@@ -431,7 +437,12 @@ struct JitShape {
   // registers one super-block ahead -- no code rows in LDS and one barrier per super-block
   bool dc = false;
   int dcw = 1;       // direct codes: 16-byte words per pattern (16 units each; 2 for up to 32 units)
+  // wave tasks (dc && nw() == 1: the waves of a workgroup share nothing after the prologue): every
+  // wave walks tasks of its own 64 * PW patterns (JArgs::n_tasks), static stride or one ticket
+  // per task from the fragment's counter -- no barrier in the loop
+  bool wt = false;
   int nw() const { return cls ? 1 : C / CW; }  // waves per pattern group
+  bool wt_ok() const { return dc && nw() == 1; }
   size_t lds_bytes() const {
     const size_t nt = (size_t)std::max(NT, 1);
     // the class exchange (root reduction, per-node rescale; the second buffer only serves the
@@ -622,6 +633,11 @@ inline std::string jit_tree4_source(const JitPlan& plan, const JitShape& sh) {
   s.reserve(4096 * events.size() + 16384);
   s += sh.ppipe ? "#define PPIPE_ 1\n" : "#define PPIPE_ 0\n";  // read by the prelude's contrib
   s += kJitPrelude;
+  if (sh.wt) {  // (JArgs::n_tasks: see the host mirror)
+    const size_t at = s.find(kJitArgsTail);
+    if (at == std::string::npos) return std::string();
+    s.replace(at, std::string(kJitArgsTail).size(), kJitArgsTailWt);
+  }
   char buf[400];
   const std::string minw_s = sh.minw > 0 ? ", " + std::to_string(sh.minw) : std::string();
   // fragment table units (CSR) as constant data of the module: unit k of fragment f is
@@ -797,7 +813,9 @@ inline std::string jit_tree4_source(const JitPlan& plan, const JitShape& sh) {
   // next super-block's
   uint4 cv_[PW_][DCW_], cvn_[PW_][DCW_];
   const uint4* dcodes = reinterpret_cast<const uint4*>(a.codes) + (i64)frag * a.n_pad * DCW_;
-  auto fetch_dc = [&](int sb_) {
+)PLKJIT";
+  if (!sh.wt)
+    s += R"PLKJIT(  auto fetch_dc = [&](int sb_) {
     const i64 q0_ = (i64)sb_ * (64 * PW_ * G_);
     const i64 pp_ = (q0_ + g * (64 * PW_) < a.n_pad ? q0_ + g * (64 * PW_) : q0_) + lane;
     if (sb_ < a.n_sblocks)
@@ -807,7 +825,24 @@ inline std::string jit_tree4_source(const JitPlan& plan, const JitShape& sh) {
   (void)cv_; (void)cvn_; (void)dcodes;
   // (issued before the table staging below: its loads overlap it)
   if (DC_) fetch_dc(blockIdx.x); else fetch_codes(blockIdx.x);
-  // The fragment's P(t) matrices, touched with wide loads while the tables stage: the
+)PLKJIT";
+  else
+    // wave tasks: the codes of the wave's own task tk_ (64 * PW_ patterns; n_pad is a multiple
+    // of the 128-pattern tile, so a task below n_tasks lies inside it).  (The address is formed
+    // in bounds for any tk_, as the super-block form does: the every-class-in-the-wave kernel
+    // then takes two registers fewer than with the bare product, 125 vs 127 in tests/jit)
+    s += R"PLKJIT(  auto fetch_dc = [&](int tk_) {
+    const i64 q0_ = (i64)tk_ * (64 * PW_);
+    const i64 pp_ = (q0_ < a.n_pad ? q0_ : 0) + lane;
+    if (tk_ < a.n_tasks)
+      _Pragma("unroll") for (int pw = 0; pw < PW_; ++pw)
+        _Pragma("unroll") for (int w_ = 0; w_ < DCW_; ++w_) cvn_[pw][w_] = dcodes[(pp_ + 64 * pw) * DCW_ + w_];
+  };
+  (void)cv_; (void)cvn_; (void)dcodes; (void)fetch_codes;
+  // (issued before the table staging below: its loads overlap it)
+  fetch_dc((int)blockIdx.x * G_ + g);
+)PLKJIT";
+  s += R"PLKJIT(  // The fragment's P(t) matrices, touched with wide loads while the tables stage: the
   // traversal reads P(t) through scalar loads one contribution ahead, and their first touch
   // (the P(t) launch wrote them through another XCD's L2) made the first super-block ~12 us
   // slower on cfg5 (34 vs 22 us; steady state 19 us)
@@ -1003,7 +1038,44 @@ inline std::string jit_tree4_source(const JitPlan& plan, const JitShape& sh) {
       if (SC_) FK[pw_] = a.scale[sl_ * a.n_pad + p + 64 * pw_]; } }
 #define SB __builtin_amdgcn_sched_barrier(0);
   asm volatile("" ::"v"(ptouch_));  // (keeps the touch loads)
-  // Super-block order.  Static: blockIdx.x, + gridDim.x, ...  Dynamic (a.dyn): the first is
+)PLKJIT";
+  if (sh.wt)
+    // Wave tasks (JitShape::wt): with direct codes and one wave per pattern group the waves of a
+    // workgroup share nothing after the prologue, so each wave walks tasks of its own 64 * PW_
+    // patterns and no barrier stands in the loop -- the waves of a SIMD drift apart and hide each
+    // other's waits, and the launch's ragged end is one task, not one super-block.  Order: the
+    // first task is blockIdx.x * G_ + g.  Static: + gridDim.x * G_, ...  Dynamic (a.dyn): lane 0
+    // takes a ticket from the fragment's counter one task ahead (the atomic's latency lies under
+    // a task's compute) and the wave reads it with readfirstlane at the top of the next task; a
+    // wave stops taking after its first index past the end.  A wave without a task skips the
+    // loop.  Which wave computes a pattern does not change its results.
+    s += R"PLKJIT(  const int nwv_ = (int)gridDim.x * G_;
+  int tk = (int)blockIdx.x * G_ + g;
+  unsigned tk_pend = 0;
+  if (a.dyn && lane == 0 && tk < a.n_tasks)
+    tk_pend = __hip_atomic_fetch_add(sbc_, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __syncthreads();  // the tables are staged (the one barrier in front of the loop)
+  for (int tk_nx = 0; tk < a.n_tasks; tk = tk_nx) {
+    const bool gv = true;
+    const i64 p0 = (i64)tk * (64 * PW_), p = p0 + lane;
+    const u8* crow = code_lds + lane;
+    (void)crow;
+    const i64 toff = (p >> 7) * (C_ * 4 * kTile) + (i64)c0 * 4 * kTile + (p & (kTile - 1));
+    (void)toff;
+    _Pragma("unroll") for (int pw = 0; pw < PW_; ++pw)
+      _Pragma("unroll") for (int w_ = 0; w_ < DCW_; ++w_) cv_[pw][w_] = cvn_[pw][w_];
+    if (a.dyn) {  // (an index outside this launch's range ends the loop)
+      const unsigned d_ = (unsigned)__builtin_amdgcn_readfirstlane((int)tk_pend);
+      tk_nx = a.n_tasks > nwv_ && d_ < (unsigned)(a.n_tasks - nwv_) ? nwv_ + (int)d_ : a.n_tasks;
+    } else {
+      tk_nx = tk + nwv_;
+    }
+    if (a.dyn && lane == 0 && tk_nx < a.n_tasks)
+      tk_pend = __hip_atomic_fetch_add(sbc_, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    fetch_dc(tk_nx);
+)PLKJIT";
+  else
+    s += R"PLKJIT(  // Super-block order.  Static: blockIdx.x, + gridDim.x, ...  Dynamic (a.dyn): the first is
   // blockIdx.x, every later one comes from the fragment's counter -- thread 0 takes the index
   // of the super-block after the next one while this one computes, so the atomic's latency is
   // hidden; a workgroup stops taking after its first index past the end.  The counter starts
@@ -1243,6 +1315,10 @@ inline std::string jit_tree4_source(const JitPlan& plan, const JitShape& sh) {
     s += "    } break;\n";
   }
   s += "    default: break;\n    }\n  }\n";
+  // wave tasks: the one barrier behind the loop.  A wave leaves the loop with every ticket
+  // atomic it issued returned (it read each at the top of the task it led to), so after this
+  // barrier every atomic of the workgroup has returned -- the exit ticket's premise
+  if (sh.wt) s += "  __syncthreads();\n";
   if (sh.clk == 1)
     s += "  if (threadIdx.x == 0) {\n"
          "    unsigned long long* q_ = clk_ + 4 * (((unsigned long long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + "
@@ -1269,12 +1345,40 @@ inline std::string jit_tree4_source(const JitPlan& plan, const JitShape& sh) {
     // PLK_DEBUG_CLOCK=2: the end stamp is taken where the super-block loop starts (the prologue:
     // code fetch, table staging, quad build), not at the kernel's end.  (Inserted into the
     // generated text, so that the ordinary programs' sources -- and their cached code -- do not change.)
-    const std::string anchor = "  for (int sb = blockIdx.x, sb_nx = 0; sb < a.n_sblocks; sb = sb_nx) {";
+    const std::string anchor = sh.wt ? "  for (int tk_nx = 0; tk < a.n_tasks; tk = tk_nx) {"
+                                     : "  for (int sb = blockIdx.x, sb_nx = 0; sb < a.n_sblocks; sb = sb_nx) {";
     const size_t at = s.find(anchor);
     if (at != std::string::npos)
       s.insert(at, "  if (threadIdx.x == 0) { unsigned long long* q_ = clk_ + 4 * (((unsigned long long)blockIdx.z * "
                    "gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x); const unsigned long long c1_ = clock64(), w1_ = "
                    "wall_clock64(); q_[0] = clk_c0_; q_[1] = clk_w0_; q_[2] = c1_; q_[3] = w1_; }\n");
+  }
+  if (sh.clk == 3) {
+    // PLK_DEBUG_CLOCK=3: every wave records, in shader-clock ticks, [0] its loop time, [1] the
+    // time between arriving at the per-super-block barrier and leaving it, summed over the
+    // rounds after the first, [2] the same for the first round (whose barrier also waits for the
+    // table staging), [3] its rounds -- one record per wave at clk_ + 4 * (workgroup * NWT_ + w).
+    // A wave-task program has no such barrier: [1] and [2] stay 0.  (Inserted as level 2 is.)
+    const std::string head = sh.wt ? "  for (int tk_nx = 0; tk < a.n_tasks; tk = tk_nx) {"
+                                   : "  for (int sb = blockIdx.x, sb_nx = 0; sb < a.n_sblocks; sb = sb_nx) {";
+    const std::string bar = "    __syncthreads();  // (DC_: also the tables' staging before the first super-block)\n";
+    const std::string tail = "    default: break;\n    }\n  }\n";
+    size_t at = s.rfind(tail);
+    if (at != std::string::npos)
+      s.insert(at + tail.size(),
+               "  if (lane == 0) { unsigned long long* q_ = clk_ + 4 * ((((unsigned long long)blockIdx.z * gridDim.y + "
+               "blockIdx.y) * gridDim.x + blockIdx.x) * NWT_ + w); q_[0] = clock64() - clk_l0_; q_[1] = clk_bw_; "
+               "q_[2] = clk_b1_; q_[3] = clk_nr_; }\n");
+    at = s.find(bar);
+    if (at != std::string::npos)
+      s.replace(at, bar.size(),
+                "    { const unsigned long long b0_ = clock64(); __syncthreads(); const unsigned long long b1_ = "
+                "clock64() - b0_; if (clk_nr_ > 1) clk_bw_ += b1_; else clk_b1_ = b1_; }\n");
+    at = s.find(head);
+    if (at != std::string::npos) {
+      s.insert(at + head.size(), " ++clk_nr_;");
+      s.insert(at, "  unsigned long long clk_bw_ = 0, clk_b1_ = 0, clk_nr_ = 0; const unsigned long long clk_l0_ = clock64();\n");
+    }
   }
   return s;
 }
