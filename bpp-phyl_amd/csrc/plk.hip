@@ -415,6 +415,11 @@ struct plk_handle_s {
   size_t clk_cap = 0;                     // workgroups the stamp buffer holds
   size_t clk_n = 0;                       // workgroups stamped by the pending traversal
   std::vector<double> clk_rec;
+  // PLK_DEBUG_CLOCK=3: the last summarised traversal's waves, [loop ticks, tasks or rounds] each in
+  // stamp order (wave w of workgroup k at k * clk_nwt + w; a launch's workgroups x-fastest of
+  // clk_gx per fragment and class) -- plk_clock_waves
+  std::vector<double> clk_waves;
+  int clk_nwt = 0, clk_gx = 0;
   int32_t* h_uflow = nullptr;             // mapped pinned: root-reduction underflow flag (plk_root_underflow)
   int32_t* d_uflow = nullptr;             // its device address
   double* h_blk_all = nullptr;            // mapped pinned: every rank's record [comm_ranks][comm_stride]
@@ -2226,6 +2231,11 @@ int update_tree4(plk_handle h, const plk_op* ops, int n_ops) {
     // (on for one class per workgroup, where the barrier wait was 22 % of a wave's loop; the
     // every-class-in-the-wave kernel waits 1.8 % there and keeps the super-block schedule)
     sh.wt = sh.wt_ok() && tune_int("JIT_WT", sh.cls ? 1 : 0, 0, 1) != 0;
+    // workgroup task pool (wave tasks only; PLK_TUNE JIT_WP=0 is the static stride, kept for A/B
+    // runs): a workgroup's waves draw its tasks (x, x + gridDim.x, ...) from one LDS counter, so
+    // every workgroup owns floor or ceil of n_tasks / gridDim.x tasks and a wave that ran slowly
+    // takes fewer of them (plk_jit.hpp)
+    sh.wp = sh.wt && tune_int("JIT_WP", sh.cls ? 1 : 0, 0, 1) != 0;
     // two patterns per lane halve the P(t) reads per FMA but double the registers:
     // measured slower (cfg2 0.255-0.301 vs 0.241 ms), so opt-in; not with speculation
     // two-stage pipeline, codes / HBM loads 3 ahead (cfg2 0.274 -> 0.259 ms); with every
@@ -2255,7 +2265,8 @@ int update_tree4(plk_handle h, const plk_op* ops, int n_ops) {
         sh.NT != h->jit_shape.NT || sh.TD != h->jit_shape.TD || sh.scale != h->jit_shape.scale || sh.L != h->jit_shape.L ||
         sh.minw != h->jit_shape.minw || sh.ppipe != h->jit_shape.ppipe || sh.clk != h->jit_shape.clk ||
         sh.cls != h->jit_shape.cls || sh.soa != h->jit_shape.soa || sh.ps1 != h->jit_shape.ps1 || sh.RD != h->jit_shape.RD ||
-        sh.dc != h->jit_shape.dc || sh.dcw != h->jit_shape.dcw || sh.wt != h->jit_shape.wt) {
+        sh.dc != h->jit_shape.dc || sh.dcw != h->jit_shape.dcw || sh.wt != h->jit_shape.wt ||
+        sh.wp != h->jit_shape.wp) {
       int rc = jit_function(h, jit_tree4_source(h->jit_plan, sh), jit_tree4_name(sh), &h->jit_fn);
       if (rc) return rc;
       h->jit_shape = sh;
@@ -2342,15 +2353,33 @@ int update_tree4(plk_handle h, const plk_op* ops, int n_ops) {
     // (PLK_DEBUG_CLOCK=3: one record per wave; a ragged last workgroup still has all its waves)
     const size_t per = h->jit_shape.clk == 3 ? (size_t)(h->n_pad / 64 + 16) * h->jit_shape.nw() : (size_t)(h->n_pad / 64);
     for (const auto& t : h->prog_tiers) need += per * t.size() * (h->jit_shape.cls ? h->C : 1);
+    // The stamps of an evaluation split over several plk_update_partials calls add up: clk_n is
+    // reset where the record is formed (clock_summary), not here.  (Traversals that never reach
+    // a root reduction would grow the buffer without end: past 64 of them the pending stamps are
+    // dropped.)
+    if (h->clk_n > 64 * need) h->clk_n = 0;
+    need += h->clk_n;
     if (need > h->clk_cap) {
-      if (h->h_clk) hipHostFree(h->h_clk);
-      h->h_clk = nullptr;
-      if (hipHostMalloc((void**)&h->h_clk, need * 4 * sizeof(unsigned long long), hipHostMallocMapped) != hipSuccess ||
-          hipHostGetDevicePointer((void**)&h->d_clk, h->h_clk, 0) != hipSuccess)
+      unsigned long long *nh = nullptr, *nd = nullptr;
+      if (hipHostMalloc((void**)&nh, need * 4 * sizeof(unsigned long long), hipHostMallocMapped) != hipSuccess ||
+          hipHostGetDevicePointer((void**)&nd, nh, 0) != hipSuccess) {
+        if (nh) hipHostFree(nh);
         return fail(h, PLK_ERR_OOM, "clock stamp buffer");
+      }
+      if (h->h_clk) {
+        if (h->clk_n) {  // the pending traversals' stamps move along, once their kernels have written them
+          if (int rc = stream_wait(h)) {
+            hipHostFree(nh);
+            return rc;
+          }
+          std::memcpy(nh, h->h_clk, h->clk_n * 4 * sizeof(unsigned long long));
+        }
+        hipHostFree(h->h_clk);
+      }
+      h->h_clk = nh;
+      h->d_clk = nd;
       h->clk_cap = need;
     }
-    h->clk_n = 0;
   }
   for (const auto& t : h->prog_tiers) {
     a.frag_start = h->d_frag + first;
@@ -2395,7 +2424,8 @@ int update_tree4(plk_handle h, const plk_op* ops, int n_ops) {
       // is 16 x the atomics on the same counter words, and at cfg2's 1 M patterns -- 7 813
       // tasks per class over 1 024 waves -- the traversal ran 388 us against 83 with the
       // super-block schedule, profiles/r07/ab_runs.md; the static stride needs none)
-      const bool dyn_on = sh.wt ? tune_is("JIT_DYN", '1') : !tune_is("JIT_DYN", '0');
+      // (a task-pool program takes its tickets from LDS: no global counter, no exit ticket)
+      const bool dyn_on = sh.wp ? false : sh.wt ? tune_is("JIT_DYN", '1') : !tune_is("JIT_DYN", '0');
       ja.dyn = (dyn_on && units >= 3 * walkers) ? 1 : 0;
       // the launch's counters start at 0; its last workgroup leaves them at 0 (exit ticket)
       ja.exit_ctr = ja.dyn ? h->d_sbctr + (size_t)h->prog_nf * h->C : nullptr;
@@ -3885,9 +3915,14 @@ void clock_summary(plk_handle h) {
     // table staging, left out of both), [1] the worst wave's share, [2] / [3] mean / longest
     // loop in shader-clock ticks, [4] waves that ran
     double ss = 0.0, worst = 0.0, sl = 0.0, ml = 0.0, n = 0.0;
+    h->clk_waves.assign(2 * h->clk_n, 0.0);  // (a wave that ran nothing keeps 0, 0)
+    h->clk_nwt = h->jit_shape.nw() * h->jit_shape.G;
+    h->clk_gx = h->jit_last_gx;
     for (size_t i = 0; i < h->clk_n; ++i) {
       const volatile unsigned long long* q = h->h_clk + 4 * i;
       if (!q[3] || q[0] <= q[2]) continue;
+      h->clk_waves[2 * i] = (double)(q[0] - q[2]);
+      h->clk_waves[2 * i + 1] = (double)q[3];
       const double loop = (double)(q[0] - q[2]), share = (double)q[1] / loop;
       ss += share;
       worst = std::max(worst, share);
@@ -4050,6 +4085,16 @@ int plk_clock_records(plk_handle h, double* out, int cap, int* n) {
   *n = have;
   if (out) std::memcpy(out, h->clk_rec.data(), (size_t)std::min(cap, have) * 5 * sizeof(double));
   if (cap >= have) h->clk_rec.clear();
+  return PLK_OK;
+}
+
+int plk_clock_waves(plk_handle h, double* out, int cap, int* n, int* waves_per_wg, int* wgs_x) {
+  if (!h || !n || cap < 0 || (cap > 0 && !out)) return fail(h, PLK_ERR_ARG, "bad clock-wave arguments");
+  const int have = (int)(h->clk_waves.size() / 2);
+  *n = have;
+  if (waves_per_wg) *waves_per_wg = h->clk_nwt;
+  if (wgs_x) *wgs_x = h->clk_gx;
+  if (out) std::memcpy(out, h->clk_waves.data(), (size_t)std::min(cap, have) * 2 * sizeof(double));
   return PLK_OK;
 }
 

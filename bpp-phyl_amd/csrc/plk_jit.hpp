@@ -441,6 +441,10 @@ struct JitShape {
   // wave walks tasks of its own 64 * PW patterns (JArgs::n_tasks), static stride or one ticket
   // per task from the fragment's counter -- no barrier in the loop
   bool wt = false;
+  // workgroup task pool (wt): workgroup x of a (fragment, class) owns tasks x, x + gridDim.x, ...
+  // (jit_pool_task) and its waves draw them from one LDS counter, whichever wave is free next --
+  // no global atomic, no barrier, no wave waiting for another
+  bool wp = false;
   int nw() const { return cls ? 1 : C / CW; }  // waves per pattern group
   bool wt_ok() const { return dc && nw() == 1; }
   size_t lds_bytes() const {
@@ -453,6 +457,14 @@ struct JitShape {
            std::max(dc ? (size_t)0 : (size_t)G * nt * 64 * PW, (size_t)QT * sizeof(double));
   }
 };
+
+// Task pool (JitShape::wp): ticket j of workgroup x of gx is this task; a ticket whose task is
+// >= n_tasks is past the workgroup's end (and so is every later one).  Every workgroup then owns
+// floor or ceil of n_tasks / gx tasks.  The generated kernel's POOL_TASK_ is this expression's text.
+#define PLK_POOL_TASK_EXPR(x, gx, j) ((x) + (j) * (gx))
+#define PLK_STR_(...) #__VA_ARGS__
+#define PLK_STR(...) PLK_STR_(__VA_ARGS__)
+inline int jit_pool_task(int x, int gx, int j) { return PLK_POOL_TASK_EXPR(x, gx, j); }
 
 // The generated kernel's name: one class per workgroup is plk_jit_tree4c, so that kernel-trace
 // statistics keep it apart from the classes-in-the-wave kernel (plk_jit_tree4) of other configs
@@ -1116,6 +1128,43 @@ inline std::string jit_tree4_source(const JitPlan& plan, const JitShape& sh) {
       sb_pend = __hip_atomic_fetch_add(sbc_, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (DC_) fetch_dc(sb_nx); else fetch_codes(sb_nx);
 )PLKJIT";
+  if (sh.wt && sh.wp) {
+    // Task pool (JitShape::wp), replaced in the wave-task text so that the programs without it
+    // keep their sources.  One LDS word per workgroup holds the next ticket: thread 0 writes G_
+    // before the barrier in front of the loop (wave g's first ticket is g, no atomic), and at the
+    // top of every task lane 0 takes the next ticket with an LDS atomic add -- there the wave's
+    // LDS / scalar-load counter is empty (the previous task ended in its root stores), so the
+    // wait before readfirstlane waits for this one return only, ~100 cycles in a task of ~10 000;
+    // the next task's codes are fetched right behind it as before.  A ticket past the end ends
+    // the wave's loop: no wave waits for another and nothing polls.  a.dyn and the fragment's
+    // global counter are not read.
+    const std::string first_wt = "  fetch_dc((int)blockIdx.x * G_ + g);\n";
+    const std::string first_wp = "#define POOL_TASK_(x, gx, j) " PLK_STR(PLK_POOL_TASK_EXPR(x, gx, j)) "\n"
+                                 "  fetch_dc(POOL_TASK_((int)blockIdx.x, (int)gridDim.x, g));\n";
+    const std::string head0 = "  const int nwv_ = (int)gridDim.x * G_;\n";
+    const std::string head1 = "  __syncthreads();  // the tables are staged (the one barrier in front of the loop)\n";
+    const std::string next0 = "    if (a.dyn) {  // (an index outside this launch's range ends the loop)\n";
+    const std::string next1 = "    fetch_dc(tk_nx);\n";
+    const size_t f0 = s.find(first_wt), h0 = s.find(head0), h1 = s.find(head1), n0 = s.find(next0),
+                 n1 = s.find(next1);
+    if (f0 == std::string::npos || h0 == std::string::npos || h1 == std::string::npos || n0 == std::string::npos ||
+        n1 == std::string::npos || !(f0 < h0 && h0 < h1 && h1 < n0 && n0 < n1))
+      return std::string();
+    // (back to front: the earlier offsets stay valid)
+    s.replace(n0, n1 - n0,
+              "    {  // (a ticket past the workgroup's last task ends the loop)\n"
+              "      unsigned j_ = 0;\n"
+              "      if (lane == 0) j_ = __hip_atomic_fetch_add(&tk_pool_, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);\n"
+              "      j_ = (unsigned)__builtin_amdgcn_readfirstlane((int)j_);\n"
+              "      tk_nx = j_ < (unsigned)a.n_tasks ? POOL_TASK_((int)blockIdx.x, (int)gridDim.x, (int)j_) : a.n_tasks;\n"
+              "    }\n");
+    s.replace(h0, h1 - h0,
+              "  __shared__ unsigned tk_pool_;  // the workgroup's next ticket\n"
+              "  if (threadIdx.x == 0) tk_pool_ = G_;\n"
+              "  int tk = POOL_TASK_((int)blockIdx.x, (int)gridDim.x, g);\n"
+              "  (void)sbc_;\n");
+    s.replace(f0, first_wt.size(), first_wp);
+  }
   int max_level = 0;
   for (const auto& ev : events)
     for (const JitEvent& e : ev) max_level = std::max(max_level, e.level);

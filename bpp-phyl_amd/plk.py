@@ -39,7 +39,7 @@ EXPORTS = [
     "plk_get_timing_ex", "plk_traversal_work", "plk_create_multi", "plk_shard_count", "plk_comm_get_id",
     "plk_comm_init", "plk_get_dpmatrix", "plk_root_pair_derivatives", "plk_get_fanout",
     "plk_root_underflow", "plk_exchange_stride", "plk_exchange_pack", "plk_exchange_reduce",
-    "plk_exchange_rank_sums", "plk_clock_records",
+    "plk_exchange_rank_sums", "plk_clock_records", "plk_clock_waves",
 ]
 
 
@@ -97,6 +97,7 @@ def load(path: str = LIB_PATH) -> ct.CDLL:
         "plk_get_fanout": ([ct.c_void_p, ct.c_int, dp, dp, P(ct.c_int64)], ct.c_int),
         "plk_root_underflow": ([ct.c_void_p, P(ct.c_int)], ct.c_int),
         "plk_clock_records": ([ct.c_void_p, dp, ct.c_int, P(ct.c_int)], ct.c_int),
+        "plk_clock_waves": ([ct.c_void_p, dp, ct.c_int, P(ct.c_int), P(ct.c_int), P(ct.c_int)], ct.c_int),
         "plk_comm_get_id": ([P(plk_comm_id)], ct.c_int),
         "plk_exchange_stride": ([P(ct.c_int64), ct.c_int, P(ct.c_int64)], ct.c_int),
         "plk_exchange_pack": ([dp, ct.c_int64, ct.c_int, ct.c_int64, dp], ct.c_int),
@@ -412,6 +413,17 @@ class Engine:
         if n.value:
             self._chk(self.lib.plk_clock_records(self.h, _d(out), n.value, ct.byref(n)))
         return out
+
+    def clock_waves(self):
+        """plk_clock_waves (PLK_DEBUG_CLOCK=3): the last summarised traversal's waves as
+        (array [workgroups, waves per workgroup, 2] of (loop ticks, tasks walked), workgroups per
+        fragment and class along x)."""
+        n, nwt, gx = ct.c_int(0), ct.c_int(0), ct.c_int(0)
+        self._chk(self.lib.plk_clock_waves(self.h, None, 0, ct.byref(n), ct.byref(nwt), ct.byref(gx)))
+        out = np.zeros((n.value, 2))
+        if n.value:
+            self._chk(self.lib.plk_clock_waves(self.h, _d(out), n.value, ct.byref(n), ct.byref(nwt), ct.byref(gx)))
+        return out.reshape(-1, max(nwt.value, 1), 2), gx.value
 
     def branch_derivatives(self, branch: int):
         """(d lnL/dt, d2 lnL/dt2) for the branch above node `branch`."""

@@ -244,6 +244,15 @@ int plk_root_underflow(plk_handle h, int* flag);
  * the held records are cleared when all fit.  Replaces nothing in the reference. */
 int plk_clock_records(plk_handle h, double* out /* cap x 5 */, int cap, int* n);
 
+/* Diagnostic (PLK_DEBUG_CLOCK=3): the waves of the last traversal that a root reduction
+ * summarised, two doubles each -- the wave's loop time in shader-clock ticks and the tasks (or
+ * super-block rounds) it walked; 0, 0 for a wave that walked none.  Stamp order: wave w of
+ * workgroup k at k * *waves_per_wg + w, the workgroups of a launch x-fastest with *wgs_x of them
+ * per fragment and class (the last launch's, where tiers differ).  *n = waves held; up to cap are
+ * copied to out.  They stay until the next summarised traversal.  Replaces nothing in the
+ * reference. */
+int plk_clock_waves(plk_handle h, double* out /* cap x 2 */, int cap, int* n, int* waves_per_wg, int* wgs_x);
+
 /* One likelihood evaluation as RHomogeneousTreeLikelihood::fireParameterChanged does it
  * (Likelihood/RHomogeneousTreeLikelihood.cpp:255-283): P(t) of the listed branches
  * (plk_update_pmatrices, P only), the postorder traversal (plk_update_partials) and the

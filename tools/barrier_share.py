@@ -12,6 +12,20 @@ ticks and the waves that ran; and the medians over the timed evaluations.
 
 With wave tasks (JIT_WT=1) the loop has no barrier: the shares are 0 and only the loop ticks
 say anything.
+
+--spread adds where the gap between the mean and the longest wave lies, from every wave's own
+loop ticks (Engine.clock_waves), per timed evaluation and as medians:
+
+  within_wg          mean over the workgroups of (longest wave - mean wave of that workgroup)
+  long_* / short_*   mean, minimum and maximum over the workgroups of the workgroup's longest
+                     wave (its last wave's end: the waves of a workgroup start the loop together),
+                     apart for the workgroups that walk R rounds under the static stride (at least
+                     one wave has R = ceil(tasks / waves) tasks there) and those that walk R - 1
+                     -- the same two sets whatever schedule ran, so before and after compare
+  longest            the loop's longest wave overall
+
+(One launch per traversal is assumed, as in config 2: with several tiers the workgroups per
+fragment are the last tier's.)
 """
 import argparse
 import json
@@ -30,28 +44,65 @@ import plk  # noqa: E402
 import workload  # noqa: E402
 
 
+def spread(waves, gx):
+    """The --spread figures of one evaluation: waves[workgroup, wave] = (loop ticks, tasks)."""
+    ticks, tasks = waves[:, :, 0], waves[:, :, 1]
+    nwg, nwt = ticks.shape
+    gx = max(gx, 1)
+    x = np.arange(nwg) % gx
+    # tasks of a (fragment, class): what its gx workgroups walked
+    n_tasks = tasks.reshape(-1, gx, nwt).sum(axis=(1, 2)).repeat(gx)
+    rounds = np.ceil(n_tasks / (gx * nwt))
+    long_wg = x * nwt < n_tasks - (rounds - 1) * gx * nwt     # wave 0 walks `rounds` under the static stride
+    ran = tasks > 0
+    live = ran.any(axis=1)
+    wg_max = ticks.max(axis=1)
+    wg_mean = np.where(live, ticks.sum(axis=1) / np.maximum(ran.sum(axis=1), 1), 0.0)
+    out = {"within_wg": float((wg_max - wg_mean)[live].mean()) if live.any() else 0.0}
+    for name, sel in (("long", live & long_wg), ("short", live & ~long_wg)):
+        v = wg_max[sel]
+        out[name + "_wgs"] = int(sel.sum())
+        out[name + "_mean"] = float(v.mean()) if v.size else 0.0
+        out[name + "_min"] = float(v.min()) if v.size else 0.0
+        out[name + "_max"] = float(v.max()) if v.size else 0.0
+    out["wave_mean"] = float(ticks[ran].mean()) if ran.any() else 0.0
+    out["longest"] = float(ticks.max()) if ticks.size else 0.0
+    out["tasks_per_wg_min"] = float(tasks.sum(axis=1)[live].min()) if live.any() else 0.0
+    out["tasks_per_wg_max"] = float(tasks.sum(axis=1).max()) if live.any() else 0.0
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="gtr_g4_dna_1M_64", choices=sorted(workload.CONFIGS))
     ap.add_argument("--patterns", type=int, default=None)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--spread", action="store_true",
+                    help="within- and between-workgroup spread of the waves' loop ticks")
     args = ap.parse_args()
     wl = workload.make_workload(args.config, n_patterns=args.patterns)
     P = wl.n_patterns
     ev = workload.Evaluator(wl, 0, 0, P, extra_flags=plk.PLK_FLAG_LNL_ONLY)
     lnl = None
-    for _ in range(args.warmup + args.steps):
+    spreads = []
+    for i in range(args.warmup + args.steps):
         lnl, _, _ = ev.step()
+        if args.spread and i >= args.warmup:
+            spreads.append(spread(*ev.eng.clock_waves()))
     rec = np.asarray(ev.eng.clock_records(), dtype=np.float64).reshape(-1, 5)
     # one record per traversal: with several tiers the last of an evaluation holds every tier's waves
     timed = rec[-args.steps:]
     med = np.median(timed, axis=0)
-    print(json.dumps({"config": args.config, "patterns": int(P), "tune": os.environ.get("PLK_TUNE", ""),
-                      "kernel_path": ev.eng.kernel_path(), "lnl": lnl,
-                      "fields": ["wait_share_mean", "wait_share_worst_wave", "loop_ticks_mean", "loop_ticks_max", "waves"],
-                      "median": [float(x) for x in med],
-                      "timed": [[float(x) for x in r] for r in timed]}))
+    out = {"config": args.config, "patterns": int(P), "tune": os.environ.get("PLK_TUNE", ""),
+           "kernel_path": ev.eng.kernel_path(), "lnl": lnl,
+           "fields": ["wait_share_mean", "wait_share_worst_wave", "loop_ticks_mean", "loop_ticks_max", "waves"],
+           "median": [float(x) for x in med],
+           "timed": [[float(x) for x in r] for r in timed]}
+    if spreads:
+        out["spread_median"] = {k: float(np.median([s[k] for s in spreads])) for k in spreads[0]}
+        out["spread_timed"] = spreads
+    print(json.dumps(out))
 
 
 if __name__ == "__main__":
