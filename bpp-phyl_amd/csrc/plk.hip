@@ -419,6 +419,7 @@ struct plk_handle_s {
   // stamp order (wave w of workgroup k at k * clk_nwt + w; a launch's workgroups x-fastest of
   // clk_gx per fragment and class) -- plk_clock_waves
   std::vector<double> clk_waves;
+  std::vector<double> clk_tails;  // per wave, in the same order: the task tail's ticks (plk_clock_wave_tails)
   int clk_nwt = 0, clk_gx = 0;
   int32_t* h_uflow = nullptr;             // mapped pinned: root-reduction underflow flag (plk_root_underflow)
   int32_t* d_uflow = nullptr;             // its device address
@@ -3916,13 +3917,17 @@ void clock_summary(plk_handle h) {
     // loop in shader-clock ticks, [4] waves that ran
     double ss = 0.0, worst = 0.0, sl = 0.0, ml = 0.0, n = 0.0;
     h->clk_waves.assign(2 * h->clk_n, 0.0);  // (a wave that ran nothing keeps 0, 0)
+    h->clk_tails.assign(h->clk_n, 0.0);
     h->clk_nwt = h->jit_shape.nw() * h->jit_shape.G;
     h->clk_gx = h->jit_last_gx;
     for (size_t i = 0; i < h->clk_n; ++i) {
       const volatile unsigned long long* q = h->h_clk + 4 * i;
-      if (!q[3] || q[0] <= q[2]) continue;
+      // ([3]: the rounds in the low 24 bits, the task tail's ticks above them)
+      const unsigned long long q3 = q[3];
+      if (!(q3 & 0xFFFFFFull) || q[0] <= q[2]) continue;
       h->clk_waves[2 * i] = (double)(q[0] - q[2]);
-      h->clk_waves[2 * i + 1] = (double)q[3];
+      h->clk_waves[2 * i + 1] = (double)(q3 & 0xFFFFFFull);
+      h->clk_tails[i] = (double)(q3 >> 24);
       const double loop = (double)(q[0] - q[2]), share = (double)q[1] / loop;
       ss += share;
       worst = std::max(worst, share);
@@ -4085,6 +4090,14 @@ int plk_clock_records(plk_handle h, double* out, int cap, int* n) {
   *n = have;
   if (out) std::memcpy(out, h->clk_rec.data(), (size_t)std::min(cap, have) * 5 * sizeof(double));
   if (cap >= have) h->clk_rec.clear();
+  return PLK_OK;
+}
+
+int plk_clock_wave_tails(plk_handle h, double* out, int cap, int* n) {
+  if (!h || !n || cap < 0 || (cap > 0 && !out)) return fail(h, PLK_ERR_ARG, "bad clock-wave arguments");
+  const int have = (int)h->clk_tails.size();
+  *n = have;
+  if (out) std::memcpy(out, h->clk_tails.data(), (size_t)std::min(cap, have) * sizeof(double));
   return PLK_OK;
 }
 

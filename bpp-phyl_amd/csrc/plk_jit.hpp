@@ -179,6 +179,13 @@ __device__ __forceinline__ unsigned long long launder_s(unsigned long long x) {
   asm volatile("" : "+s"(x));
   return x;
 }
+// a wave-uniform double as a scalar-register value (both words through readfirstlane)
+__device__ __forceinline__ double uniform_d(double x) {
+  const unsigned long long b = (unsigned long long)__double_as_longlong(x);
+  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)b);
+  const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(b >> 32));
+  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
 // component j of a uint4 (j a constant)
 __device__ __forceinline__ unsigned cvw(const uint4& v, int j) { return j == 0 ? v.x : j == 1 ? v.y : j == 2 ? v.z : v.w; }
 // Table element x of row r (R rows per class block): [row][4] or, with SOA_, [half][row][2]
@@ -277,22 +284,26 @@ __device__ __forceinline__ void rescale(double (&v)[4 * CW * PW], int (&cnt)[PW]
 // t_c = (sum_s L[c][s] pi_s, terms <= 0 dropped under the guards) * prob_c -- reduce_root's
 // t[pw][0] -- goes to cls_sum[c][p]; class_sums_to_blocks adds the classes in class order with
 // the guard or clamp, takes the log and forms the block sums as reduce_root + wave_sums_to_blocks.
+// pi[0..3] and prob come in as values (uniform_d, read once per launch in front of the loop):
+// read through a's pointers here they are reloaded for every task, one vector load at a time
+// behind its own wait -- the loop stores through a.cls_sum, so nothing proves them invariant.
 template <int PW>
-__device__ __forceinline__ void reduce_root_cls(const JArgs& a, const double (&acc)[4 * PW], int c0, i64 p, bool gv) {
+__device__ __forceinline__ void reduce_root_cls(const JArgs& a, const double (&acc)[4 * PW], const double (&pi)[4],
+                                                double prob, int c0, i64 p, bool gv) {
   if (!gv) return;
 #pragma unroll
   for (int pw = 0; pw < PW; ++pw) {
     double lc = 0.0;
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
-      const double li = acc[4 * pw + s] * a.pi[s];
+      const double li = acc[4 * pw + s] * pi[s];
       if (a.guard) {
         if (li > 0.0) lc += li;
       } else {
         lc += li;
       }
     }
-    __builtin_nontemporal_store(lc * a.probs[c0], a.cls_sum + (i64)c0 * a.n_pad + p + 64 * pw);
+    __builtin_nontemporal_store(lc * prob, a.cls_sum + (i64)c0 * a.n_pad + p + 64 * pw);
   }
 }
 
@@ -1067,16 +1078,47 @@ inline std::string jit_tree4_source(const JitPlan& plan, const JitShape& sh) {
   if (a.dyn && lane == 0 && tk < a.n_tasks)
     tk_pend = __hip_atomic_fetch_add(sbc_, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   __syncthreads();  // the tables are staged (the one barrier in front of the loop)
-  for (int tk_nx = 0; tk < a.n_tasks; tk = tk_nx) {
+)PLKJIT";
+  // One class per workgroup: the root constants, read once per launch (never part of the source:
+  // pi and the class probabilities change between evaluations without a recompile)
+  static const char* kRootConst = R"PLKJIT(  // reduce_root_cls's pi and this class's probability, wave-uniform values for the whole launch
+  double rpi_[4];
+  _Pragma("unroll") for (int s_ = 0; s_ < 4; ++s_) rpi_[s_] = uniform_d(a.pi[s_]);
+  const double rpr_ = uniform_d(a.probs[c0]);
+)PLKJIT";
+  // ... and with wave tasks the code rotation (the prefetched codes of the next task become the
+  // current ones) stands at the END of a task, in front of its root-term stores, with the wait
+  // for the prefetch pinned there (ROT_): a wait at the top of the next task would also wait for
+  // the stores just issued (one counter for vector loads and stores), once per task
+  const bool rot_end = sh.wt && sh.cls;
+  // (pinned: the 32-bit words that hold a unit's code, unit k in byte k -- the others are never read)
+  if (rot_end) {
+    s += kRootConst;
+    s += "#define ROT_ { _Pragma(\"unroll\") for (int pw = 0; pw < PW_; ++pw) { \\\n"
+         "    _Pragma(\"unroll\") for (int w_ = 0; w_ < DCW_; ++w_) cv_[pw][w_] = cvn_[pw][w_]; \\\n"
+         "    asm volatile(\"\" : ";
+    const int nwords = std::min((std::max(sh.NT, 1) + 3) / 4, 4 * sh.dcw);
+    for (int j = 0; j < nwords; ++j) {
+      snprintf(buf, sizeof(buf), "%s\"+v\"(cv_[pw][%d].%c)", j ? ", " : "", j >> 2, "xyzw"[j & 3]);
+      s += buf;
+    }
+    s += "); } }\n  ROT_  // the first task's codes\n";
+  }
+  if (sh.wt)
+    s += R"PLKJIT(  for (int tk_nx = 0; tk < a.n_tasks; tk = tk_nx) {
     const bool gv = true;
     const i64 p0 = (i64)tk * (64 * PW_), p = p0 + lane;
     const u8* crow = code_lds + lane;
     (void)crow;
     const i64 toff = (p >> 7) * (C_ * 4 * kTile) + (i64)c0 * 4 * kTile + (p & (kTile - 1));
     (void)toff;
-    _Pragma("unroll") for (int pw = 0; pw < PW_; ++pw)
+)PLKJIT";
+  if (sh.wt && !rot_end)
+    s += R"PLKJIT(    _Pragma("unroll") for (int pw = 0; pw < PW_; ++pw)
       _Pragma("unroll") for (int w_ = 0; w_ < DCW_; ++w_) cv_[pw][w_] = cvn_[pw][w_];
-    if (a.dyn) {  // (an index outside this launch's range ends the loop)
+)PLKJIT";
+  if (sh.wt)
+    s += R"PLKJIT(    if (a.dyn) {  // (an index outside this launch's range ends the loop)
       const unsigned d_ = (unsigned)__builtin_amdgcn_readfirstlane((int)tk_pend);
       tk_nx = a.n_tasks > nwv_ && d_ < (unsigned)(a.n_tasks - nwv_) ? nwv_ + (int)d_ : a.n_tasks;
     } else {
@@ -1087,7 +1129,7 @@ inline std::string jit_tree4_source(const JitPlan& plan, const JitShape& sh) {
     fetch_dc(tk_nx);
 )PLKJIT";
   else
-    s += R"PLKJIT(  // Super-block order.  Static: blockIdx.x, + gridDim.x, ...  Dynamic (a.dyn): the first is
+    s += std::string(sh.cls ? kRootConst : "") + R"PLKJIT(  // Super-block order.  Static: blockIdx.x, + gridDim.x, ...  Dynamic (a.dyn): the first is
   // blockIdx.x, every later one comes from the fragment's counter -- thread 0 takes the index
   // of the super-block after the next one while this one computes, so the atomic's latency is
   // hidden; a workgroup stops taking after its first index past the end.  The counter starts
@@ -1240,6 +1282,7 @@ inline std::string jit_tree4_source(const JitPlan& plan, const JitShape& sh) {
       if (ev[i].op == T_LOAD || ev[i].op == T_ASCEND) cev.push_back(i);
     auto emit_body = [&](bool exact) {
       s += "      kzero(K0);\n";
+      bool rotated = false;  // rot_end: the code rotation is out (once per pass, at the root event)
       size_t kc = 0;   // contributions emitted
       int pbase = 0;   // buffer of the next contribution's class 0
       if (pstream && !cev.empty()) {
@@ -1342,16 +1385,20 @@ inline std::string jit_tree4_source(const JitPlan& plan, const JitShape& sh) {
           s += "      SB\n";
         } else {  // T_ROOT
           if (sh.scale) check_line(0);
+          // (the task's last code was read above: the rotation and its wait, then the stores)
+          if (rot_end && !rotated) s += "      ROT_\n";
+          rotated = true;
           if (e.a >= 0) {
             snprintf(buf, sizeof(buf), "      store<CW_, PW_, SC_>(a, %s, toff, p, c0, A0, K0, gv);\n",
                      sref(e.a).c_str());
             s += buf;
           }
           if (e.b)
-            s += sh.cls ? "      reduce_root_cls<PW_>(a, A0, c0, p, gv);\n"
+            s += sh.cls ? "      reduce_root_cls<PW_>(a, A0, rpi_, rpr_, c0, p, gv);\n"
                         : "      reduce_root<C_, CW_, PW_, NWT_, SC_>(a, A0, K0, xch, w, g, c0, p0, p, gv);\n";
         }
       }
+      if (rot_end && !rotated) s += "      ROT_\n";  // (a pass without a root event)
     };
     for (size_t q = f; q < events.size(); ++q)
       if (leader[q] == (int)f) {
@@ -1408,6 +1455,9 @@ inline std::string jit_tree4_source(const JitPlan& plan, const JitShape& sh) {
     // rounds after the first, [2] the same for the first round (whose barrier also waits for the
     // table staging), [3] its rounds -- one record per wave at clk_ + 4 * (workgroup * NWT_ + w).
     // A wave-task program has no such barrier: [1] and [2] stay 0.  (Inserted as level 2 is.)
+    // One class per workgroup: [3] also carries the task tail above its low 24 bits (the rounds) --
+    // the ticks from the end of a task's last contraction (the stamp in front of the code rotation
+    // and reduce_root_cls) to the top of the next task, or to the loop's end, summed over the tasks.
     const std::string head = sh.wt ? "  for (int tk_nx = 0; tk < a.n_tasks; tk = tk_nx) {"
                                    : "  for (int sb = blockIdx.x, sb_nx = 0; sb < a.n_sblocks; sb = sb_nx) {";
     const std::string bar = "    __syncthreads();  // (DC_: also the tables' staging before the first super-block)\n";
@@ -1415,9 +1465,18 @@ inline std::string jit_tree4_source(const JitPlan& plan, const JitShape& sh) {
     size_t at = s.rfind(tail);
     if (at != std::string::npos)
       s.insert(at + tail.size(),
+               "  if (clk_t0_) clk_tl_ += clock64() - clk_t0_;\n"
                "  if (lane == 0) { unsigned long long* q_ = clk_ + 4 * ((((unsigned long long)blockIdx.z * gridDim.y + "
                "blockIdx.y) * gridDim.x + blockIdx.x) * NWT_ + w); q_[0] = clock64() - clk_l0_; q_[1] = clk_bw_; "
-               "q_[2] = clk_b1_; q_[3] = clk_nr_; }\n");
+               "q_[2] = clk_b1_; q_[3] = (clk_nr_ & 0xFFFFFFull) | (clk_tl_ << 24); }\n");
+    // (the tail's start: in front of every root reduction and, where it stands there, its rotation)
+    const std::string red = "      reduce_root_cls<PW_>(", rot = "      ROT_\n";
+    for (at = s.find(red); at != std::string::npos; at = s.find(red, at + red.size())) {
+      if (at >= rot.size() && s.compare(at - rot.size(), rot.size(), rot) == 0) at -= rot.size();
+      const std::string stamp = "      clk_t0_ = clock64();\n";
+      s.insert(at, stamp);
+      at += stamp.size() + rot.size();
+    }
     at = s.find(bar);
     if (at != std::string::npos)
       s.replace(at, bar.size(),
@@ -1425,8 +1484,9 @@ inline std::string jit_tree4_source(const JitPlan& plan, const JitShape& sh) {
                 "clock64() - b0_; if (clk_nr_ > 1) clk_bw_ += b1_; else clk_b1_ = b1_; }\n");
     at = s.find(head);
     if (at != std::string::npos) {
-      s.insert(at + head.size(), " ++clk_nr_;");
-      s.insert(at, "  unsigned long long clk_bw_ = 0, clk_b1_ = 0, clk_nr_ = 0; const unsigned long long clk_l0_ = clock64();\n");
+      s.insert(at + head.size(), " ++clk_nr_; if (clk_t0_) { clk_tl_ += clock64() - clk_t0_; clk_t0_ = 0; }");
+      s.insert(at, "  unsigned long long clk_bw_ = 0, clk_b1_ = 0, clk_nr_ = 0, clk_tl_ = 0, clk_t0_ = 0; "
+                   "const unsigned long long clk_l0_ = clock64();\n");
     }
   }
   return s;

@@ -39,7 +39,7 @@ EXPORTS = [
     "plk_get_timing_ex", "plk_traversal_work", "plk_create_multi", "plk_shard_count", "plk_comm_get_id",
     "plk_comm_init", "plk_get_dpmatrix", "plk_root_pair_derivatives", "plk_get_fanout",
     "plk_root_underflow", "plk_exchange_stride", "plk_exchange_pack", "plk_exchange_reduce",
-    "plk_exchange_rank_sums", "plk_clock_records", "plk_clock_waves",
+    "plk_exchange_rank_sums", "plk_clock_records", "plk_clock_waves", "plk_clock_wave_tails",
 ]
 
 
@@ -98,6 +98,7 @@ def load(path: str = LIB_PATH) -> ct.CDLL:
         "plk_root_underflow": ([ct.c_void_p, P(ct.c_int)], ct.c_int),
         "plk_clock_records": ([ct.c_void_p, dp, ct.c_int, P(ct.c_int)], ct.c_int),
         "plk_clock_waves": ([ct.c_void_p, dp, ct.c_int, P(ct.c_int), P(ct.c_int), P(ct.c_int)], ct.c_int),
+        "plk_clock_wave_tails": ([ct.c_void_p, dp, ct.c_int, P(ct.c_int)], ct.c_int),
         "plk_comm_get_id": ([P(plk_comm_id)], ct.c_int),
         "plk_exchange_stride": ([P(ct.c_int64), ct.c_int, P(ct.c_int64)], ct.c_int),
         "plk_exchange_pack": ([dp, ct.c_int64, ct.c_int, ct.c_int64, dp], ct.c_int),
@@ -414,16 +415,22 @@ class Engine:
             self._chk(self.lib.plk_clock_records(self.h, _d(out), n.value, ct.byref(n)))
         return out
 
-    def clock_waves(self):
+    def clock_waves(self, tail: bool = False):
         """plk_clock_waves (PLK_DEBUG_CLOCK=3): the last summarised traversal's waves as
         (array [workgroups, waves per workgroup, 2] of (loop ticks, tasks walked), workgroups per
-        fragment and class along x)."""
+        fragment and class along x).  tail=True: a third column, the wave's task-tail ticks
+        (plk_clock_wave_tails: root reduction and code rotation, summed over its tasks)."""
         n, nwt, gx = ct.c_int(0), ct.c_int(0), ct.c_int(0)
         self._chk(self.lib.plk_clock_waves(self.h, None, 0, ct.byref(n), ct.byref(nwt), ct.byref(gx)))
         out = np.zeros((n.value, 2))
         if n.value:
             self._chk(self.lib.plk_clock_waves(self.h, _d(out), n.value, ct.byref(n), ct.byref(nwt), ct.byref(gx)))
-        return out.reshape(-1, max(nwt.value, 1), 2), gx.value
+        if tail:
+            t = np.zeros(n.value)
+            if n.value:
+                self._chk(self.lib.plk_clock_wave_tails(self.h, _d(t), n.value, ct.byref(n)))
+            out = np.concatenate([out, t[:, None]], axis=1)
+        return out.reshape(-1, max(nwt.value, 1), out.shape[1]), gx.value
 
     def branch_derivatives(self, branch: int):
         """(d lnL/dt, d2 lnL/dt2) for the branch above node `branch`."""

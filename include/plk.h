@@ -253,6 +253,14 @@ int plk_clock_records(plk_handle h, double* out /* cap x 5 */, int cap, int* n);
  * reference. */
 int plk_clock_waves(plk_handle h, double* out /* cap x 2 */, int cap, int* n, int* waves_per_wg, int* wgs_x);
 
+/* Diagnostic (PLK_DEBUG_CLOCK=3, one class per workgroup): the same waves in the same order, one
+ * double each -- the wave's task tail in shader-clock ticks, summed over its tasks: from the end
+ * of a task's last contraction (in front of the root reduction and the rotation of the
+ * prefetched codes) to the top of the next task, or to the end of the loop.  The kernel's record
+ * keeps its four 64-bit words per wave: the tail travels in the fourth, above the rounds' 24
+ * bits.  *n = waves held; up to cap are copied to out.  Replaces nothing in the reference. */
+int plk_clock_wave_tails(plk_handle h, double* out /* cap */, int cap, int* n);
+
 /* One likelihood evaluation as RHomogeneousTreeLikelihood::fireParameterChanged does it
  * (Likelihood/RHomogeneousTreeLikelihood.cpp:255-283): P(t) of the listed branches
  * (plk_update_pmatrices, P only), the postorder traversal (plk_update_partials) and the

@@ -24,6 +24,15 @@ loop ticks (Engine.clock_waves), per timed evaluation and as medians:
                      -- the same two sets whatever schedule ran, so before and after compare
   longest            the loop's longest wave overall
 
+--tail adds the task tail's share of a wave's loop (one class per workgroup; Engine.clock_waves
+with tail=True): the ticks between the end of a task's last contraction and the top of the next
+task -- the root reduction and the rotation of the prefetched codes -- summed over the wave's
+tasks, over the wave's loop ticks:
+
+  tail_share_mean / _worst   mean over the waves that ran / the worst wave
+  tail_ticks_per_task        tail ticks of all waves over the tasks they walked
+  task_ticks                 loop ticks of all waves over the same tasks
+
 (One launch per traversal is assumed, as in config 2: with several tiers the workgroups per
 fragment are the last tier's.)
 """
@@ -72,6 +81,18 @@ def spread(waves, gx):
     return out
 
 
+def tail(waves, gx):
+    """The --tail figures of one evaluation: waves[workgroup, wave] = (loop ticks, tasks, tail ticks)."""
+    ticks, tasks, tl = waves[:, :, 0], waves[:, :, 1], waves[:, :, 2]
+    ran = tasks > 0
+    if not ran.any():
+        return {"tail_share_mean": 0.0, "tail_share_worst": 0.0, "tail_ticks_per_task": 0.0, "task_ticks": 0.0}
+    share = tl[ran] / ticks[ran]
+    return {"tail_share_mean": float(share.mean()), "tail_share_worst": float(share.max()),
+            "tail_ticks_per_task": float(tl[ran].sum() / tasks[ran].sum()),
+            "task_ticks": float(ticks[ran].sum() / tasks[ran].sum())}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="gtr_g4_dna_1M_64", choices=sorted(workload.CONFIGS))
@@ -80,16 +101,20 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--spread", action="store_true",
                     help="within- and between-workgroup spread of the waves' loop ticks")
+    ap.add_argument("--tail", action="store_true",
+                    help="the task tail's (root reduction, code rotation) share of a wave's loop")
     args = ap.parse_args()
     wl = workload.make_workload(args.config, n_patterns=args.patterns)
     P = wl.n_patterns
     ev = workload.Evaluator(wl, 0, 0, P, extra_flags=plk.PLK_FLAG_LNL_ONLY)
     lnl = None
-    spreads = []
+    spreads, tails = [], []
     for i in range(args.warmup + args.steps):
         lnl, _, _ = ev.step()
         if args.spread and i >= args.warmup:
             spreads.append(spread(*ev.eng.clock_waves()))
+        if args.tail and i >= args.warmup:
+            tails.append(tail(*ev.eng.clock_waves(tail=True)))
     rec = np.asarray(ev.eng.clock_records(), dtype=np.float64).reshape(-1, 5)
     # one record per traversal: with several tiers the last of an evaluation holds every tier's waves
     timed = rec[-args.steps:]
@@ -102,6 +127,9 @@ def main():
     if spreads:
         out["spread_median"] = {k: float(np.median([s[k] for s in spreads])) for k in spreads[0]}
         out["spread_timed"] = spreads
+    if tails:
+        out["tail_median"] = {k: float(np.median([t[k] for t in tails])) for k in tails[0]}
+        out["tail_timed"] = tails
     print(json.dumps(out))
 
 
