@@ -13,6 +13,7 @@
 #include "plk_jit.hpp"
 #include "plk_jitm.hpp"
 #include "plk_dr.hpp"
+#include "plk_post.hpp"
 #include "plk_exchange.hpp"
 
 #include <hip/hip_runtime.h>
@@ -384,6 +385,16 @@ struct plk_handle_s {
   double* dr_blk = nullptr;
   size_t dr_blk_cap = 0;
   double* dr_out = nullptr;
+  // node posteriors (plk_post.hpp).  U is current while state_epoch -- counted up by every call
+  // that changes a P(t), a partial, a tip code, pi or the rates -- still is what the last
+  // preorder pass saw.
+  uint64_t state_epoch = 1;
+  uint64_t dr_u_epoch = 0;              // state_epoch of the last preorder pass (0: none)
+  bool dr_u_pi = false;                 // that pass folded pi into the U of the root's sons
+  PostNode* d_post = nullptr;
+  size_t d_post_cap = 0;
+  char* post_buf = nullptr;             // staged outputs of one chunk of nodes (kPostStageCap)
+  size_t post_buf_cap = 0;
   // multi-device handle (plk_create_multi): one shard handle per device over contiguous,
   // block-aligned pattern ranges; the parent owns no device memory
   std::vector<plk_handle> shards;
@@ -1156,7 +1167,7 @@ int plk_destroy(plk_handle h) {
                   h->d_ops, h->wave_sums, h->d_links, h->d_opsl, h->d_prog, h->d_frag, h->d1_sums,
                   h->d2_sums, h->d_dprog, h->pmatsT, h->d_ucodes, h->d_units, h->d_cherry3,
                   h->d_cherry_tips, h->d_cherry, h->d_drb, h->d_drm, h->dr_blk, h->dr_out, h->d_drpre, h->d_sbctr,
-                  h->d_cherry_rows, h->d_kidsl, h->d_cls, h->d_ucodes_dc, h->d_units_start};
+                  h->d_cherry_rows, h->d_kidsl, h->d_cls, h->d_ucodes_dc, h->d_units_start, h->d_post, h->post_buf};
   for (void* p : bufs)
     if (p) hipFree(p);
   if (h->h_req) (void)hipHostFree(h->h_req);
@@ -1285,6 +1296,7 @@ int plk_set_code_table(plk_handle h, int n_codes, const double* code_to_vec) {
   h->n_codes_table = n_codes;
   h->code_map.resize(256, -1);
   h->table_set = true;
+  h->state_epoch++;
   return upload_compact_table(h);
 }
 
@@ -1323,6 +1335,7 @@ int plk_set_tip_codes(plk_handle h, int tip, const uint8_t* codes) {
   hipSetDevice(h->device);
   HIPCHK(h, hipMemcpy(h->codes + (size_t)tip * h->n_pad, cc.data(), (size_t)h->n_patterns, hipMemcpyHostToDevice));
   h->tip_set[tip] = 1;
+  h->state_epoch++;
   h->ucodes_valid = false;
   h->cherry_codes_valid = false;
   return PLK_OK;
@@ -1348,6 +1361,7 @@ int plk_set_category_rates(plk_handle h, const double* rates, const double* prob
   HIPCHK(h, hipMemcpy(h->rates, rates, h->C * sizeof(double), hipMemcpyHostToDevice));
   HIPCHK(h, hipMemcpy(h->probs, probs, h->C * sizeof(double), hipMemcpyHostToDevice));
   h->rates_set = true;
+  h->state_epoch++;
   h->fused_lnl_valid = false;  // a cached fused root reduction used the old class probabilities
   return PLK_OK;
 }
@@ -1360,6 +1374,7 @@ int plk_set_root_frequencies(plk_handle h, const double* pi) {
   HIPCHK(h, hipStreamSynchronize(h->stream));
   HIPCHK(h, hipMemcpy(h->pi, pi, h->S * sizeof(double), hipMemcpyHostToDevice));
   h->pi_set = true;
+  h->state_epoch++;
   h->fused_lnl_valid = false;  // a cached fused root reduction used the old frequencies
   return PLK_OK;
 }
@@ -1394,6 +1409,7 @@ int plk_update_pmatrices(plk_handle h, int n, const int32_t* branch, const int32
     if (!h->eigen_set[m]) return fail(h, PLK_ERR_STATE, "eigen system %d not set", m);
     if (!(t[i] >= 0.0)) return fail(h, PLK_ERR_ARG, "branch length %g not >= 0", t[i]);
   }
+  h->state_epoch++;
   hipSetDevice(h->device);
   const size_t S2 = (size_t)h->S * h->S;
   if ((deriv_mask & PLK_DERIV_DP) && !h->dpmats) {
@@ -1573,6 +1589,7 @@ int plk_set_pmatrix(plk_handle h, int branch, const double* P) {
   const size_t n = (size_t)h->C * h->S * h->S;
   HIPCHK(h, hipMemcpy(h->pmats + (size_t)branch * n, P, n * sizeof(double), hipMemcpyHostToDevice));
   h->pmat_valid[branch] = 1;
+  h->state_epoch++;
   h->pmatsT_dirty = true;
   if (!h->deriv_valid.empty()) h->deriv_valid[branch] = 0;
   if (branch < h->n_tips) h->tip_table_valid[branch] = 0;
@@ -3566,7 +3583,13 @@ int dr_derivatives(plk_handle h, double* d1, double* d2) {
   for (size_t d = 0; pre && d < depth.size(); ++d)
     for (int f : depth[d])
       if (f >= nt && (h->topo_kids[f].size() < 2 || h->topo_kids[f].size() > 3)) pre = false;
-  if (pre) return dr_fused_preorder(h, depth, parent, root, d1, d2);
+  h->dr_u_epoch = 0;
+  if (pre) {
+    if ((rc = dr_fused_preorder(h, depth, parent, root, d1, d2))) return rc;
+    h->dr_u_epoch = h->state_epoch;  // (pi sits in the U of the root's sons)
+    h->dr_u_pi = true;
+    return PLK_OK;
+  }
   // M_f for every internal father below the root
   std::vector<int2> mlist;
   for (size_t d = 1; d < depth.size(); ++d)
@@ -3719,9 +3742,200 @@ int dr_derivatives(plk_handle h, double* d1, double* d2) {
   HIPCHK(h, hipStreamSynchronize(h->stream));
   if (d1) std::copy(out.begin(), out.begin() + nn, d1);
   if (d2) std::copy(out.begin() + nn, out.end(), d2);
+  h->dr_u_epoch = h->state_epoch;
+  h->dr_u_pi = false;
   return PLK_OK;
 }
 
+// ---------------------------------------------------------------------------
+// Node posteriors (plk_post.hpp): J = p_c (P_v^T u) (*) L_v over the requested nodes, one
+// launch per chunk of nodes.  Outputs are staged on the device row-wise and turned into the
+// caller's [node][pattern][...] order here; the staging of a chunk stays under
+// kPostStageCap, so a request for every node of a large handle runs in several launches
+// instead of allocating its whole answer on the device.
+// ---------------------------------------------------------------------------
+constexpr size_t kPostStageCap = (size_t)256 << 20;
+
+// total / p0: patterns per node of the caller's arrays and this handle's first pattern in
+// them (a shard of a multi-device handle fills its range)
+int node_posteriors_local(plk_handle h, int n_nodes, const int32_t* nodes, double* joint, double* state_post,
+                          double* class_post, uint8_t* best_state, int64_t total, int64_t p0) {
+  if (n_nodes <= 0 || !nodes) return fail(h, PLK_ERR_ARG, "bad node list (%d nodes)", n_nodes);
+  if (!joint && !state_post && !class_post && !best_state) return fail(h, PLK_ERR_ARG, "no output requested");
+  const int S = h->S, C = h->C, nt = h->n_tips, nn = h->n_nodes;
+  for (int i = 0; i < n_nodes; ++i)
+    if (nodes[i] < nt || nodes[i] >= nn) return fail(h, PLK_ERR_ARG, "node %d is not an internal node", nodes[i]);
+  if (h->trav_ops.empty()) return fail(h, PLK_ERR_STATE, "no traversal yet (plk_update_partials)");
+  std::vector<int> parent(nn, -1);
+  for (int n = 0; n < nn; ++n)
+    for (int c : h->topo_kids[n]) parent[c] = n;
+  int root = h->trav_ops.back().parent;
+  while (parent[root] >= 0) root = parent[root];
+  std::vector<char> in_tree(nn, 0);
+  {
+    std::vector<int> st(1, root);
+    while (!st.empty()) {
+      const int n = st.back();
+      st.pop_back();
+      in_tree[n] = 1;
+      for (int c : h->topo_kids[n]) st.push_back(c);
+    }
+  }
+  bool root_only = true;
+  for (int i = 0; i < n_nodes; ++i) {
+    if (!in_tree[nodes[i]]) return fail(h, PLK_ERR_ARG, "node %d is not in the current tree", nodes[i]);
+    if (nodes[i] != root) root_only = false;
+  }
+  if (!root_only && !(h->flags & PLK_FLAG_DOUBLE_RECURSIVE))
+    return fail(h, PLK_ERR_STATE, "handle was not created with PLK_FLAG_DOUBLE_RECURSIVE (only the root is served)");
+  if (!h->pi_set || !h->rates_set) return fail(h, PLK_ERR_STATE, "root frequencies / category rates not set");
+  if (!(S == 2 || S == 3 || S == 4 || S == 20 || S == 64))
+    return fail(h, PLK_ERR_UNSUPPORTED, "state count %d has no kernel instance", S);
+  hipSetDevice(h->device);
+  int rc;
+  bool restore = false;
+  if (!root_only) {
+    // the preorder pass, unless the last one still holds
+    if (h->dr_u_epoch != h->state_epoch && (rc = dr_derivatives(h, nullptr, nullptr))) return rc;
+  } else if (!h->materialized[root - nt]) {
+    // an lnL-only traversal kept the root in registers: write every partial (the same
+    // arithmetic), and afterwards run the caller's traversal again as it was, so that the
+    // handle -- kernel path, fused root reduction, underflow flag -- is left as found
+    if ((rc = materialize_last_traversal(h))) return rc;
+    if (!h->materialized[root - nt]) return fail(h, PLK_ERR_STATE, "root %d has no partial", root);
+    restore = true;
+  }
+  // a compressed slot holds one entry per distinct subtree pattern (root-only requests)
+  const std::vector<int32_t>* ids = nullptr;
+  if ((h->flags & PLK_FLAG_SUBTREE_PATTERNS) && h->cmp_valid && !h->slots_expanded && !h->cmp_ids[root - nt].empty())
+    ids = &h->cmp_ids[root - nt];
+  const int CS = C * S;
+  const size_t rows = (joint ? CS : 0) + (state_post ? S : 0) + (class_post ? C : 0);
+  const size_t per_node = (size_t)h->n_pad * (rows * sizeof(double) + (best_state ? 1 : 0));
+  const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_nodes, kPostStageCap / per_node));
+  if ((rc = ensure_cap(h, (void**)&h->post_buf, &h->post_buf_cap, (size_t)chunk * per_node))) return rc;
+  if ((rc = ensure_cap(h, (void**)&h->d_post, &h->d_post_cap, (size_t)chunk * sizeof(PostNode)))) return rc;
+  std::vector<double> hbuf;
+  std::vector<uint8_t> hbest;
+  const bool mfma = S == 20 || S == 64;
+  for (int n0 = 0; n0 < n_nodes; n0 += chunk) {
+    const int cn = std::min(chunk, n_nodes - n0);
+    std::vector<PostNode> pn((size_t)cn);
+    for (int i = 0; i < cn; ++i) {
+      const int v = nodes[n0 + i];
+      PostNode& q = pn[(size_t)i];
+      std::memset(&q, 0, sizeof(q));
+      q.node = v;
+      q.lslot = v - nt;
+      q.is_root = v == root;
+      q.uslot = q.is_root ? q.lslot : h->dr_slot0 + v;
+      q.use_pi = !q.is_root && parent[v] == root && !h->dr_u_pi;
+    }
+    HIPCHK(h, hipMemcpyAsync(h->d_post, pn.data(), pn.size() * sizeof(PostNode), hipMemcpyHostToDevice, h->stream));
+    PostArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.partials = h->partials;
+    a.pmats = h->pmats;
+    a.pi = h->pi;
+    a.probs = h->probs;
+    double* d = (double*)h->post_buf;
+    if (joint) a.joint = d, d += (size_t)cn * CS * h->n_pad;
+    if (state_post) a.spost = d, d += (size_t)cn * S * h->n_pad;
+    if (class_post) a.cpost = d, d += (size_t)cn * C * h->n_pad;
+    if (best_state) a.best = (uint8_t*)d;
+    a.slot_stride = h->slot_stride;
+    a.n_pad = h->n_pad;
+    a.C = C;
+    a.n_blk = (int)(h->n_pad / 64);
+    a.G = (size_t)C * S * S * sizeof(double) <= 64 * 1024 ? C : 1;
+    EventPair ev;
+    if (h->timing & PLK_TIME_PARTIALS) {
+      ev = get_events(h, 0);
+      hipEventRecord(ev.a, h->stream);
+    }
+    if (mfma && tune_int("POST_VALU", 0, 0, 1)) {
+      const dim3 grid((unsigned)(h->n_pad / kPostThreads), (unsigned)cn);
+      const size_t lds = (size_t)S * S * sizeof(double);
+      if (S == 20)
+        post_valu_kernel<20><<<grid, kPostThreads, lds, h->stream>>>(h->d_post, a);
+      else
+        post_valu_kernel<64><<<grid, kPostThreads, lds, h->stream>>>(h->d_post, a);
+    } else if (mfma) {
+      // a few workgroups per node, each looping over 64-pattern blocks (8192 in total)
+      const unsigned gx = (unsigned)std::min<int64_t>(a.n_blk, std::max<int64_t>(1, (8192 + cn - 1) / cn));
+      const size_t lds = (size_t)a.G * S * S * sizeof(double);
+      if (S == 20)
+        post_mfma_kernel<20><<<dim3(gx, (unsigned)cn), kPostThreads, lds, h->stream>>>(h->d_post, a);
+      else
+        post_mfma_kernel<64><<<dim3(gx, (unsigned)cn), kPostThreads, lds, h->stream>>>(h->d_post, a);
+    } else {
+      const dim3 grid((unsigned)(h->n_pad / kPostThreads), (unsigned)cn);
+#define PLK_POST_S(S_)                                                                              \
+  switch (C) {                                                                                      \
+    case 1: post_s4_kernel<S_, 1><<<grid, kPostThreads, 0, h->stream>>>(h->d_post, a); break;       \
+    case 2: post_s4_kernel<S_, 2><<<grid, kPostThreads, 0, h->stream>>>(h->d_post, a); break;       \
+    case 3: post_s4_kernel<S_, 3><<<grid, kPostThreads, 0, h->stream>>>(h->d_post, a); break;       \
+    case 4: post_s4_kernel<S_, 4><<<grid, kPostThreads, 0, h->stream>>>(h->d_post, a); break;       \
+    default: post_s4_kernel<S_, 0><<<grid, kPostThreads, 0, h->stream>>>(h->d_post, a); break;      \
+  }
+      switch (S) {
+        case 2: PLK_POST_S(2) break;
+        case 3: PLK_POST_S(3) break;
+        case 4: PLK_POST_S(4) break;
+      }
+#undef PLK_POST_S
+    }
+    HIPCHK(h, hipGetLastError());
+    if (h->timing & PLK_TIME_PARTIALS) {
+      hipEventRecord(ev.b, h->stream);
+      h->events.push_back(ev);
+      h->n_launches++;
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    // rows [node][k][n_pad] -> the caller's [node][pattern][k]
+    auto rows_out = [&](const double* dev, int K, double* out) -> int {
+      hbuf.resize((size_t)cn * K * h->n_pad);
+      HIPCHK(h, hipMemcpy(hbuf.data(), dev, hbuf.size() * sizeof(double), hipMemcpyDeviceToHost));
+      for (int i = 0; i < cn; ++i) {
+        double* o = out + ((size_t)(n0 + i) * total + p0) * K;
+        const double* src = hbuf.data() + (size_t)i * K * h->n_pad;
+        for (int64_t p = 0; p < h->n_patterns; ++p) {
+          const int64_t j = ids ? (*ids)[(size_t)p] : p;
+          for (int k = 0; k < K; ++k) o[p * K + k] = src[(size_t)k * h->n_pad + j];
+        }
+      }
+      return PLK_OK;
+    };
+    if (joint && (rc = rows_out(a.joint, CS, joint))) return rc;
+    if (state_post && (rc = rows_out(a.spost, S, state_post))) return rc;
+    if (class_post && (rc = rows_out(a.cpost, C, class_post))) return rc;
+    if (best_state) {
+      for (int i = 0; i < cn; ++i) {
+        uint8_t* o = best_state + (size_t)(n0 + i) * total + p0;
+        const uint8_t* src = a.best + (size_t)i * h->n_pad;
+        if (!ids) {
+          HIPCHK(h, hipMemcpy(o, src, (size_t)h->n_patterns, hipMemcpyDeviceToHost));
+        } else {
+          hbest.resize((size_t)h->n_pad);
+          HIPCHK(h, hipMemcpy(hbest.data(), src, hbest.size(), hipMemcpyDeviceToHost));
+          for (int64_t p = 0; p < h->n_patterns; ++p) o[p] = hbest[(size_t)(*ids)[(size_t)p]];
+        }
+      }
+    }
+  }
+  if (restore) {
+    const std::vector<plk_op> ops = h->trav_ops;
+    const int n_ops = (int)ops.size();
+    if (h->flags & PLK_FLAG_SUBTREE_PATTERNS)
+      rc = update_compressed(h, ops.data(), n_ops);
+    else if (tree4_supported(h) && fusable(ops.data(), n_ops))
+      rc = update_tree4(h, ops.data(), n_ops);
+    else
+      rc = update_levelwise(h, ops.data(), n_ops);
+    if (rc) return rc;
+  }
+  return PLK_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -3731,6 +3945,7 @@ int plk_update_partials(plk_handle h, const plk_op* ops, int n_ops) {
   if (h && !h->shards.empty()) return multi_each(h, [&](plk_handle x) { return plk_update_partials(x, ops, n_ops); });
   if (!h || n_ops < 0 || (n_ops > 0 && !ops)) return fail(h, PLK_ERR_ARG, "bad op list");
   if (n_ops == 0) return PLK_OK;
+  h->state_epoch++;
   hipSetDevice(h->device);
   // the last call's list again (an optimiser's evaluations): its checks hold still -- every
   // condition validate_ops tests is monotonic (matrices, tip codes) except the partial an
@@ -4442,6 +4657,22 @@ int plk_all_branch_derivatives(plk_handle h, double* d1, double* d2) {
   if (d1) std::memcpy(d1, v.data(), n * sizeof(double));
   if (d2) std::memcpy(d2, v.data() + n, n * sizeof(double));
   return PLK_OK;
+}
+
+int plk_node_posteriors(plk_handle h, int n_nodes, const int32_t* nodes, double* joint, double* state_post,
+                        double* class_post, uint8_t* best_state) {
+  env_refresh();
+  if (!h) return fail(h, PLK_ERR_ARG, "null handle");
+  if (!h->shards.empty()) {
+    if (n_nodes <= 0 || !nodes) return fail(h, PLK_ERR_ARG, "bad node list (%d nodes)", n_nodes);
+    if (!joint && !state_post && !class_post && !best_state) return fail(h, PLK_ERR_ARG, "no output requested");
+    // every shard fills its pattern range of the caller's arrays
+    return multi_slices(h, [&](plk_handle x, int64_t a) {
+      return node_posteriors_local(x, n_nodes, nodes, joint, state_post, class_post, best_state, h->n_patterns, a);
+    });
+  }
+  // (under a communicator: the rank's own patterns, no collective call)
+  return node_posteriors_local(h, n_nodes, nodes, joint, state_post, class_post, best_state, h->n_patterns, 0);
 }
 
 const char* plk_kernel_path(plk_handle h) {

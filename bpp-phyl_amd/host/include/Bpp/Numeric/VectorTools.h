@@ -1,4 +1,4 @@
-// bpp-core VectorTools subset: element-wise vector arithmetic operators and vectorUnion.
+// bpp-core VectorTools subset: element-wise vector arithmetic operators, vectorUnion, sum, whichMax.
 #ifndef BPP_AMD_VECTORTOOLS_H
 #define BPP_AMD_VECTORTOOLS_H
 
@@ -33,6 +33,14 @@ struct VectorTools {
     for (const T& x : v2)
       if (std::find(out.begin(), out.end(), x) == out.end()) out.push_back(x);
     return out;
+  }
+  // index of the first of the largest elements (0 for an empty vector)
+  template <class T>
+  static size_t whichMax(const std::vector<T>& v) {
+    size_t best = 0;
+    for (size_t i = 1; i < v.size(); i++)
+      if (v[i] > v[best]) best = i;
+    return best;
   }
   template <class T>
   static T sum(const std::vector<T>& v) {

@@ -225,6 +225,36 @@ class AbstractPlkTreeLikelihood : public virtual TreeLikelihood {
   // Partial likelihoods of a node in the reference's [pattern][class][state] order.
   VVVdouble getLikelihoodArray(int nodeId) const;
   plk_handle_s* getEngine() const { return engine_; }
+  // Posterior rate classes (AbstractDiscreteRatesAcrossSitesTreeLikelihood): per site, from
+  // the root's partials alone (plk_node_posteriors on the root: any engine, any traversal
+  // mode, nothing of the evaluation state disturbed).
+  VVdouble getPosteriorProbabilitiesOfEachRate() const;              // [site][class]
+  Vdouble getPosteriorRateOfEachSite() const;                        // sum_c r_c post_c
+  std::vector<size_t> getRateClassWithMaxPostProbOfEachSite() const;
+  // Node posteriors per distinct pattern, flat in the engine's order: joint
+  // [node][pattern][class][state], statePost [node][pattern][state], classPost
+  // [node][pattern][class], best [node][pattern].  Nodes other than the root need a
+  // double-recursive likelihood; dP / d2P are brought up to date first.
+  struct NodePosteriors {
+    std::vector<double> joint, statePost, classPost;
+    std::vector<unsigned char> best;
+  };
+  NodePosteriors computeNodePosteriors(const std::vector<int>& nodeIds, bool joint, bool states, bool classes,
+                                       bool best) const;
+  bool isLeafNode(int nodeId) const { return tree_->getNode(nodeId)->isLeaf(); }
+  std::vector<int> getInnerNodesId() const;
+  // a leaf's init values per distinct pattern, [pattern][state]
+  // (DRASDRTreeLikelihoodData::getLeafLikelihoods)
+  VVdouble getLeafLikelihoods(int nodeId) const;
+  // a leaf's observed states per distinct pattern
+  const std::vector<int>& getLeafPatternStates(int nodeId) const;
+  const std::vector<size_t>& getRootArrayPositions() const { return rootPatternLinks_; }
+  const DiscreteDistribution* getRateDistribution() const { return rateDistribution_; }
+  const Alphabet* getAlphabet() const { return data_ ? data_->getAlphabet() : nullptr; }
+  const SubstitutionModel* getModelForNode(int nodeId) const {
+    const Node* n = tree_->getNode(nodeId);
+    return modelForIndex(n->hasFather() ? modelIndexForNode(n) : modelIndexForNode(n->getSon(0)));
+  }
   // what the evaluations since construction did on the engine (host counters, no device call)
   const EvaluationStats& getEvaluationStats() const { return stats_; }
 };

@@ -40,6 +40,7 @@ EXPORTS = [
     "plk_comm_init", "plk_get_dpmatrix", "plk_root_pair_derivatives", "plk_get_fanout",
     "plk_root_underflow", "plk_exchange_stride", "plk_exchange_pack", "plk_exchange_reduce",
     "plk_exchange_rank_sums", "plk_clock_records", "plk_clock_waves", "plk_clock_wave_tails",
+    "plk_node_posteriors",
 ]
 
 
@@ -128,6 +129,7 @@ def load(path: str = LIB_PATH) -> ct.CDLL:
         "plk_branch_derivatives": ([ct.c_void_p, ct.c_int, dp, dp], ct.c_int),
         "plk_root_pair_derivatives": ([ct.c_void_p, ct.c_int, ct.c_int, ct.c_double, ct.c_double, dp, dp], ct.c_int),
         "plk_all_branch_derivatives": ([ct.c_void_p, dp, dp], ct.c_int),
+        "plk_node_posteriors": ([ct.c_void_p, ct.c_int, ip, dp, dp, dp, P(ct.c_uint8)], ct.c_int),
         "plk_kernel_path": ([ct.c_void_p], ct.c_char_p),
         "plk_compressed_work": ([ct.c_void_p, P(ct.c_int64)], ct.c_int),
         "plk_evaluate": ([ct.c_void_p, ct.c_int, ip, ip, dp, P(plk_op), ct.c_int, ct.c_int, dp, dp], ct.c_int),
@@ -452,6 +454,31 @@ class Engine:
         d1, d2 = np.zeros(n), np.zeros(n)
         self._chk(self.lib.plk_all_branch_derivatives(self.h, _d(d1), _d(d2)))
         return d1, d2
+
+    def node_posteriors(self, nodes, joint: bool = False, states: bool = True, classes: bool = False,
+                        best: bool = True) -> dict:
+        """plk_node_posteriors for the internal nodes `nodes` of the last traversal: a dict with
+        the requested arrays -- "joint" [node, pattern, class, state], "states" [node, pattern,
+        state], "classes" [node, pattern, class] and "best" [node, pattern] (uint8, the lowest
+        index among the maxima of "states"; 255 where the site likelihood underflowed).  Nodes
+        other than the root need PLK_FLAG_DOUBLE_RECURSIVE and dP / d2P of every branch."""
+        nd = np.ascontiguousarray(nodes, dtype=np.int32).ravel()
+        n = len(nd)
+        out = {}
+        if joint:
+            out["joint"] = np.empty((n, self.P, self.C, self.S))
+        if states:
+            out["states"] = np.empty((n, self.P, self.S))
+        if classes:
+            out["classes"] = np.empty((n, self.P, self.C))
+        if best:
+            out["best"] = np.empty((n, self.P), dtype=np.uint8)
+        self._chk(self.lib.plk_node_posteriors(
+            self.h, n, nd.ctypes.data_as(ct.POINTER(ct.c_int32)),
+            _d(out["joint"]) if joint else None, _d(out["states"]) if states else None,
+            _d(out["classes"]) if classes else None,
+            out["best"].ctypes.data_as(ct.POINTER(ct.c_uint8)) if best else None))
+        return out
 
     def set_timing(self, on: bool):
         self._chk(self.lib.plk_set_timing(self.h, (PLK_TIME_PARTIALS | PLK_TIME_PMAT | PLK_TIME_ROOT) if on is True

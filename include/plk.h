@@ -311,6 +311,37 @@ int plk_root_pair_derivatives(plk_handle h, int a, int b, double alpha, double b
  * support; not with PLK_FLAG_SUBTREE_PATTERNS. */
 int plk_all_branch_derivatives(plk_handle h, double* d1, double* d2);
 
+/* Marginal posteriors of internal nodes for the tree of the last plk_update_partials call: per
+ * pattern and node v, with up_v[c][x] = sum_y U_v[c][y] P_v[c][y][x] (pi folded in as in
+ * plk_all_branch_derivatives),
+ *   J_v[c][x] = p_c up_v[c][x] L_v[c][x]   (the root: p_c pi_x L_r[c][x]),   l = sum_c sum_x J_v[c][x],
+ *   joint = J / l,  state_post[x] = sum_c joint,  class_post[c] = sum_x joint,
+ *   best_state = the lowest index among the maxima of state_post.
+ * Each output may be NULL (not all four).  A pattern whose l is not a positive finite number (an
+ * unscaled underflow) gets probabilities 0 and best_state 255; no error is reported.  Scale
+ * counts cancel in J / l, so scaled and unscaled handles answer alike.
+ * Replaces MarginalAncestralStateReconstruction::getAncestralStatesForNode
+ * (Likelihood/MarginalAncestralStateReconstruction.cpp), DRTreeLikelihoodTools::
+ * getPosteriorProbabilitiesForEachStateForEachRate (Likelihood/DRTreeLikelihoodTools.cpp) and
+ * AbstractDiscreteRatesAcrossSitesTreeLikelihood::getPosteriorProbabilitiesOfEachRate
+ * (Likelihood/AbstractDiscreteRatesAcrossSitesTreeLikelihood.cpp).  Deviation: p_c is always in J
+ * (the true posterior); DRTreeLikelihoodTools leaves it out at internal nodes, which is the same
+ * thing whenever the class probabilities are equal.
+ * Preconditions and error codes are those of plk_all_branch_derivatives; its preorder pass is run
+ * here, unless no P(t), partial, tip code, pi or rate has changed since the last one.  A request that names only the root needs none of them -- no PLK_FLAG_DOUBLE_RECURSIVE,
+ * no dP/d2P, no preorder pass, any traversal mode -- and leaves plk_kernel_path, the partials and
+ * the next plk_root_loglik as they were (after an lnL-only traversal the partials are written as
+ * plk_get_partials does, then the traversal is run once more as it was).
+ * PLK_ERR_ARG: a tip, an index out of range, a node outside the current tree, n_nodes <= 0, all
+ * outputs NULL.  A multi-device handle fills the caller's arrays shard by shard (bitwise the
+ * single-device result); under a communicator a rank returns its own patterns, with no
+ * collective call.  Device staging is bounded (256 MiB): longer node lists run in chunks. */
+int plk_node_posteriors(plk_handle h, int n_nodes, const int32_t* nodes,
+                        double* joint /* n_nodes x n_patterns x C x S, or NULL */,
+                        double* state_post /* n_nodes x n_patterns x S, or NULL */,
+                        double* class_post /* n_nodes x n_patterns x C, or NULL */,
+                        uint8_t* best_state /* n_nodes x n_patterns, or NULL */);
+
 /* Instrumentation: HIP-event timing on the handle's stream of the kernels selected
  * by the mask given to plk_set_timing (0 = off).  Each timed launch adds an event
  * pair to the stream, so time only what is needed. */
