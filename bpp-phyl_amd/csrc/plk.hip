@@ -14,6 +14,7 @@
 #include "plk_jitm.hpp"
 #include "plk_dr.hpp"
 #include "plk_post.hpp"
+#include "plk_map.hpp"
 #include "plk_exchange.hpp"
 
 #include <hip/hip_runtime.h>
@@ -395,6 +396,21 @@ struct plk_handle_s {
   size_t d_post_cap = 0;
   char* post_buf = nullptr;             // staged outputs of one chunk of nodes (kPostStageCap)
   size_t post_buf_cap = 0;
+  // substitution mapping (plk_map.hpp).  Count matrices are no input of U or L, so a call that
+  // changes them leaves state_epoch alone.
+  int count_T = 0;                      // types per model (0: none yet; fixed by the first call)
+  std::vector<std::vector<double> > count_B;  // per model: B [T][S][S] (empty: no types)
+  std::vector<char> count_G_dirty;      // per model: G_k predates B or the eigen system
+  double* count_G = nullptr;            // [model][T][S][S]
+  double* wmats = nullptr;              // [node][T][C][S][S]
+  std::vector<char> wmat_valid;         // per node
+  std::vector<uint64_t> tipu_epoch;     // per tip: state_epoch its U slot was filled for (0: never)
+  MapBranch* d_mapb = nullptr;
+  size_t d_mapb_cap = 0;
+  double* map_blk = nullptr;            // workgroup sums, then the root-block sums, of one chunk
+  size_t map_blk_cap = 0;
+  char* d_mapreq = nullptr;             // a count-matrix request: t, branch, model
+  size_t d_mapreq_cap = 0;
   // multi-device handle (plk_create_multi): one shard handle per device over contiguous,
   // block-aligned pattern ranges; the parent owns no device memory
   std::vector<plk_handle> shards;
@@ -1167,7 +1183,8 @@ int plk_destroy(plk_handle h) {
                   h->d_ops, h->wave_sums, h->d_links, h->d_opsl, h->d_prog, h->d_frag, h->d1_sums,
                   h->d2_sums, h->d_dprog, h->pmatsT, h->d_ucodes, h->d_units, h->d_cherry3,
                   h->d_cherry_tips, h->d_cherry, h->d_drb, h->d_drm, h->dr_blk, h->dr_out, h->d_drpre, h->d_sbctr,
-                  h->d_cherry_rows, h->d_kidsl, h->d_cls, h->d_ucodes_dc, h->d_units_start, h->d_post, h->post_buf};
+                  h->d_cherry_rows, h->d_kidsl, h->d_cls, h->d_ucodes_dc, h->d_units_start, h->d_post, h->post_buf,
+                  h->count_G, h->wmats, h->d_mapb, h->map_blk, h->d_mapreq};
   for (void* p : bufs)
     if (p) hipFree(p);
   if (h->h_req) (void)hipHostFree(h->h_req);
@@ -1391,6 +1408,7 @@ int plk_set_eigen(plk_handle h, int model, const double* V, const double* Vinv, 
   HIPCHK(h, hipMemcpy(h->Vinv + model * S2, Vinv, S2 * sizeof(double), hipMemcpyHostToDevice));
   HIPCHK(h, hipMemcpy(h->lambda + (size_t)model * h->S, lambda, h->S * sizeof(double), hipMemcpyHostToDevice));
   h->eigen_set[model] = 1;
+  if (!h->count_G_dirty.empty()) h->count_G_dirty[model] = 1;
   return PLK_OK;
 }
 
@@ -3936,6 +3954,309 @@ int node_posteriors_local(plk_handle h, int n_nodes, const int32_t* nodes, doubl
   }
   return PLK_OK;
 }
+
+// ---------------------------------------------------------------------------
+// Substitution mapping (plk_map.hpp): count matrices W^k_v and the per-branch counts.
+// ---------------------------------------------------------------------------
+
+// The handle's type count is fixed by the first call that names one; W is allocated then.
+int map_fix_types(plk_handle h, int n_types) {
+  if (n_types < 1 || n_types > kMapMaxTypes) return fail(h, PLK_ERR_ARG, "n_types %d not in [1, %d]", n_types, kMapMaxTypes);
+  if (h->count_T && h->count_T != n_types)
+    return fail(h, PLK_ERR_ARG, "the handle holds %d substitution types, not %d", h->count_T, n_types);
+  if (!h->wmats) {
+    hipSetDevice(h->device);
+    int rc = dalloc(h, (void**)&h->wmats, (size_t)h->n_nodes * n_types * h->C * h->S * h->S * sizeof(double));
+    if (rc) return rc;
+    h->wmat_valid.assign(h->n_nodes, 0);
+    h->count_B.assign(h->n_models, std::vector<double>());
+    h->count_G_dirty.assign(h->n_models, 0);
+  }
+  h->count_T = n_types;
+  return PLK_OK;
+}
+
+// G_k = Vinv B_k V of one model, on the host from the device's eigen system
+int map_form_G(plk_handle h, int model) {
+  const int S = h->S, T = h->count_T;
+  const size_t SS = (size_t)S * S;
+  std::vector<double> V(SS), Vi(SS), G((size_t)T * SS), tmp(SS);
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, hipMemcpy(V.data(), h->V + model * SS, SS * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(h, hipMemcpy(Vi.data(), h->Vinv + model * SS, SS * sizeof(double), hipMemcpyDeviceToHost));
+  for (int k = 0; k < T; ++k) {
+    const double* B = h->count_B[model].data() + k * SS;
+    for (int i = 0; i < S; ++i)
+      for (int y = 0; y < S; ++y) {
+        double s = 0.0;
+        for (int x = 0; x < S; ++x) s += Vi[i * S + x] * B[x * S + y];
+        tmp[i * S + y] = s;
+      }
+    for (int i = 0; i < S; ++i)
+      for (int j = 0; j < S; ++j) {
+        double s = 0.0;
+        for (int y = 0; y < S; ++y) s += tmp[i * S + y] * V[y * S + j];
+        G[k * SS + i * S + j] = s;
+      }
+  }
+  if (!h->count_G) {
+    int rc = dalloc(h, (void**)&h->count_G, (size_t)h->n_models * kMapMaxTypes * SS * sizeof(double));
+    if (rc) return rc;
+  }
+  HIPCHK(h, hipMemcpy(h->count_G + (size_t)model * T * SS, G.data(), G.size() * sizeof(double), hipMemcpyHostToDevice));
+  h->count_G_dirty[model] = 0;
+  return PLK_OK;
+}
+
+// U_v of the requested tip branches, which neither preorder form keeps: the levelwise op
+// U_v = (M_f U_f) (*) prod_{siblings s} (P_s L_s) into the slot dr_slot0 + v, rescaling
+// included.  pi is left out at the root's sons (the map kernels multiply it in); below them
+// M_f carries it exactly when U_f leaves it out, the rule of the levelwise preorder, so the
+// matrices written here are the ones that pass writes.  A tip is filled once per state_epoch.
+int map_fill_tip_uppers(plk_handle h, const std::vector<int>& tips, const std::vector<int>& parent, int root) {
+  const int nt = h->n_tips, nn = h->n_nodes, S = h->S, C = h->C;
+  if (h->tipu_epoch.empty()) h->tipu_epoch.assign(nt, 0);
+  std::vector<int> todo;
+  for (int v : tips)
+    if (h->tipu_epoch[v] != h->state_epoch && std::find(todo.begin(), todo.end(), v) == todo.end()) todo.push_back(v);
+  if (todo.empty()) return PLK_OK;
+  int rc;
+  if ((rc = refresh_tip_tables(h))) return rc;
+  const bool mfma = S == 20 || S == 64;
+  if (mfma && (rc = ensure_pmatsT(h))) return rc;
+  const int mat_base = nn + kScratchMats;
+  std::vector<int2> mlist;
+  for (int v : todo) {
+    const int f = parent[v];
+    const int2 e = make_int2(f, parent[f] == root && !h->dr_u_pi ? 1 : 0);
+    if (f != root && std::find_if(mlist.begin(), mlist.end(), [&](const int2& o) { return o.x == f; }) == mlist.end())
+      mlist.push_back(e);
+  }
+  if (!mlist.empty()) {
+    if ((rc = ensure_cap(h, (void**)&h->d_drm, &h->d_drm_cap, mlist.size() * sizeof(int2)))) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->d_drm, mlist.data(), mlist.size() * sizeof(int2), hipMemcpyHostToDevice, h->stream));
+    dr_matrix_kernel<<<dim3((unsigned)mlist.size(), C), 256, 0, h->stream>>>(h->pmats, h->pmats, mfma ? h->pmatsT : nullptr,
+                                                                           h->pi, h->d_drm, mat_base, C, S);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));  // mlist is read by the copy
+  }
+  // ops of at most three children; the rest of a larger father accumulates in later launches
+  std::vector<std::vector<KOp> > chunks;
+  for (int v : todo) {
+    const int f = parent[v];
+    std::vector<int> ck_tip, ck_child, ck_branch;
+    if (f != root) {
+      ck_tip.push_back(0);
+      ck_child.push_back(h->dr_slot0 + f);
+      ck_branch.push_back(mat_base + f);
+    }
+    for (int s : h->topo_kids[f])
+      if (s != v) {
+        ck_tip.push_back(s < nt);
+        ck_child.push_back(s < nt ? s : s - nt);
+        ck_branch.push_back(s);
+      }
+    for (size_t k0 = 0, j = 0; k0 < ck_tip.size(); k0 += 3, ++j) {
+      KOp op;
+      std::memset(&op, 0, sizeof(op));
+      op.parent = h->dr_slot0 + v;
+      op.flags = k0 == 0 ? 0 : PLK_OP_ACCUMULATE;
+      for (size_t k = k0; k < ck_tip.size() && k < k0 + 3; ++k) {
+        const int i = op.n++;
+        op.is_tip[i] = ck_tip[k];
+        op.child[i] = ck_child[k];
+        op.branch[i] = ck_branch[k];
+      }
+      if (chunks.size() <= j) chunks.resize(j + 1);
+      chunks[j].push_back(op);
+    }
+  }
+  std::vector<KOp> flat;
+  std::vector<std::pair<size_t, int> > launches;
+  for (auto& ch : chunks) {
+    launches.push_back(std::make_pair(flat.size(), (int)ch.size()));
+    flat.insert(flat.end(), ch.begin(), ch.end());
+  }
+  if ((rc = ensure_cap(h, (void**)&h->d_ops, &h->d_ops_cap, flat.size() * sizeof(KOp)))) return rc;
+  HIPCHK(h, hipMemcpyAsync(h->d_ops, flat.data(), flat.size() * sizeof(KOp), hipMemcpyHostToDevice, h->stream));
+  h->last_ops.clear();  // d_ops now holds these ops
+  for (auto& l : launches) {
+    EventPair ev;
+    if (h->timing & PLK_TIME_PARTIALS) {
+      ev = get_events(h, 0);
+      hipEventRecord(ev.a, h->stream);
+    }
+    if ((rc = launch_partials_ops(h, h->d_ops + l.first, l.second))) return rc;
+    if (h->timing & PLK_TIME_PARTIALS) {
+      hipEventRecord(ev.b, h->stream);
+      h->events.push_back(ev);
+      h->n_launches++;
+    }
+  }
+  HIPCHK(h, hipStreamSynchronize(h->stream));  // flat is read by the copy
+  for (int v : todo) h->tipu_epoch[v] = h->state_epoch;
+  return PLK_OK;
+}
+
+// counts: [branch][total][T] with this handle's patterns from p0; blocks: [branch][T][nB_total]
+// sums of w count per kRootBlock patterns, this handle's blocks from B0 (either may be null)
+int branch_counts_local(plk_handle h, int n_branches, const int32_t* branches, double* counts, double* blocks,
+                        int64_t total, int64_t p0, int64_t nB_total, int64_t B0) {
+  if (n_branches <= 0 || !branches) return fail(h, PLK_ERR_ARG, "bad branch list (%d branches)", n_branches);
+  if (!counts && !blocks) return fail(h, PLK_ERR_ARG, "no output requested");
+  const int S = h->S, C = h->C, nt = h->n_tips, nn = h->n_nodes;
+  for (int i = 0; i < n_branches; ++i)
+    if (branches[i] < 0 || branches[i] >= nn) return fail(h, PLK_ERR_ARG, "branch %d out of range", branches[i]);
+  if (h->flags & PLK_FLAG_SUBTREE_PATTERNS)
+    return fail(h, PLK_ERR_UNSUPPORTED, "substitution mapping reads full-length partials (no pattern compression)");
+  if (!(h->flags & PLK_FLAG_DOUBLE_RECURSIVE))
+    return fail(h, PLK_ERR_STATE, "handle was not created with PLK_FLAG_DOUBLE_RECURSIVE");
+  if (h->trav_ops.empty()) return fail(h, PLK_ERR_STATE, "no traversal yet (plk_update_partials)");
+  std::vector<int> parent(nn, -1);
+  for (int n = 0; n < nn; ++n)
+    for (int c : h->topo_kids[n]) parent[c] = n;
+  int root = h->trav_ops.back().parent;
+  while (parent[root] >= 0) root = parent[root];
+  std::vector<char> in_tree(nn, 0);
+  {
+    std::vector<int> st(1, root);
+    while (!st.empty()) {
+      const int n = st.back();
+      st.pop_back();
+      in_tree[n] = 1;
+      for (int c : h->topo_kids[n]) st.push_back(c);
+    }
+  }
+  for (int i = 0; i < n_branches; ++i) {
+    if (branches[i] == root) return fail(h, PLK_ERR_ARG, "node %d is the root (it has no branch)", root);
+    if (!in_tree[branches[i]]) return fail(h, PLK_ERR_ARG, "node %d is not in the current tree", branches[i]);
+  }
+  const int T = h->count_T;
+  for (int i = 0; i < n_branches; ++i)
+    if (!T || !h->wmat_valid[branches[i]])
+      return fail(h, PLK_ERR_STATE, "branch %d has no count matrix (plk_update_count_matrices / plk_set_count_matrix)",
+                  branches[i]);
+  hipSetDevice(h->device);
+  int rc;
+  // the preorder pass, unless the last one still holds
+  if (h->dr_u_epoch != h->state_epoch && (rc = dr_derivatives(h, nullptr, nullptr))) return rc;
+  std::vector<int> tips;
+  for (int i = 0; i < n_branches; ++i)
+    if (branches[i] < nt) tips.push_back(branches[i]);
+  if ((rc = map_fill_tip_uppers(h, tips, parent, root))) return rc;
+  const bool mfma = S == 20 || S == 64;
+  const int sub = mfma ? 64 : kMapThreads;                 // patterns per workgroup sum
+  const int n_blk = (int)(h->n_pad / sub), per = kRootBlock / sub;
+  const int nB = h->n_blocks;
+  // staging per branch: the per-pattern rows when they are asked for, else the workgroup sums
+  const size_t per_branch = (size_t)T * (counts ? (size_t)h->n_pad : (size_t)(n_blk + nB)) * sizeof(double);
+  const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_branches, kPostStageCap / per_branch));
+  if (counts && (rc = ensure_cap(h, (void**)&h->post_buf, &h->post_buf_cap, (size_t)chunk * per_branch))) return rc;
+  if ((rc = ensure_cap(h, (void**)&h->d_mapb, &h->d_mapb_cap, (size_t)chunk * sizeof(MapBranch)))) return rc;
+  if (blocks && (rc = ensure_cap(h, (void**)&h->map_blk, &h->map_blk_cap, (size_t)chunk * T * (n_blk + nB) * sizeof(double))))
+    return rc;
+  std::vector<double> hbuf;
+  for (int n0 = 0; n0 < n_branches; n0 += chunk) {
+    const int cn = std::min(chunk, n_branches - n0);
+    std::vector<MapBranch> mb((size_t)cn);
+    for (int i = 0; i < cn; ++i) {
+      const int v = branches[n0 + i];
+      MapBranch& q = mb[(size_t)i];
+      std::memset(&q, 0, sizeof(q));
+      q.node = v;
+      q.is_tip = v < nt;
+      q.child = v < nt ? v : v - nt;
+      q.uslot = h->dr_slot0 + v;
+      // (the U of a tip son of the root is the one filled above: always without pi)
+      q.use_pi = parent[v] == root && (v < nt || !h->dr_u_pi);
+    }
+    HIPCHK(h, hipMemcpyAsync(h->d_mapb, mb.data(), mb.size() * sizeof(MapBranch), hipMemcpyHostToDevice, h->stream));
+    MapArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.partials = h->partials;
+    a.codes = h->codes;
+    a.code_table = h->code_table;
+    a.pmats = h->pmats;
+    a.wmats = h->wmats;
+    a.pi = h->pi;
+    a.probs = h->probs;
+    a.weights = h->weights;
+    a.counts = counts ? (double*)h->post_buf : nullptr;
+    a.blk = blocks ? h->map_blk : nullptr;
+    a.slot_stride = h->slot_stride;
+    a.n_pad = h->n_pad;
+    a.n_patterns = h->n_patterns;
+    a.C = C;
+    a.T = T;
+    a.n_blk = n_blk;
+    const int NM = (T + 1) * C;
+    a.G = (int)std::min<size_t>((size_t)NM, std::max<size_t>(1, (size_t)64 * 1024 / ((size_t)S * S * sizeof(double))));
+    EventPair ev;
+    if (h->timing & PLK_TIME_PARTIALS) {
+      ev = get_events(h, 0);
+      hipEventRecord(ev.a, h->stream);
+    }
+    if (mfma) {
+      // a few workgroups per branch, each looping over 64-pattern blocks (8192 in total)
+      const unsigned gx = (unsigned)std::min<int64_t>(n_blk, std::max<int64_t>(1, (8192 + cn - 1) / cn));
+      const size_t lds = (size_t)a.G * S * S * sizeof(double);
+      if (S == 20)
+        map_mfma_kernel<20><<<dim3(gx, (unsigned)cn), kMapThreads, lds, h->stream>>>(h->d_mapb, a);
+      else
+        map_mfma_kernel<64><<<dim3(gx, (unsigned)cn), kMapThreads, lds, h->stream>>>(h->d_mapb, a);
+    } else {
+      const dim3 grid((unsigned)n_blk, (unsigned)cn);
+#define PLK_MAP_S(S_)                                                                            \
+  switch (C) {                                                                                   \
+    case 1: map_s4_kernel<S_, 1><<<grid, kMapThreads, 0, h->stream>>>(h->d_mapb, a); break;      \
+    case 2: map_s4_kernel<S_, 2><<<grid, kMapThreads, 0, h->stream>>>(h->d_mapb, a); break;      \
+    case 3: map_s4_kernel<S_, 3><<<grid, kMapThreads, 0, h->stream>>>(h->d_mapb, a); break;      \
+    case 4: map_s4_kernel<S_, 4><<<grid, kMapThreads, 0, h->stream>>>(h->d_mapb, a); break;      \
+    default: map_s4_kernel<S_, 0><<<grid, kMapThreads, 0, h->stream>>>(h->d_mapb, a); break;     \
+  }
+      switch (S) {
+        case 2: PLK_MAP_S(2) break;
+        case 3: PLK_MAP_S(3) break;
+        case 4: PLK_MAP_S(4) break;
+      }
+#undef PLK_MAP_S
+    }
+    HIPCHK(h, hipGetLastError());
+    if (h->timing & PLK_TIME_PARTIALS) {
+      hipEventRecord(ev.b, h->stream);
+      h->events.push_back(ev);
+      h->n_launches++;
+    }
+    double* d_out = nullptr;
+    if (blocks) {
+      d_out = h->map_blk + (size_t)cn * T * n_blk;
+      const int n_rows = cn * T;
+      map_blocks_kernel<<<(unsigned)((n_rows * nB + 255) / 256), 256, 0, h->stream>>>(h->map_blk, d_out, n_rows, n_blk, per, nB);
+      HIPCHK(h, hipGetLastError());
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (counts) {
+      // rows [branch][k][n_pad] -> the caller's [branch][pattern][k]
+      hbuf.resize((size_t)cn * T * h->n_pad);
+      HIPCHK(h, hipMemcpy(hbuf.data(), a.counts, hbuf.size() * sizeof(double), hipMemcpyDeviceToHost));
+      for (int i = 0; i < cn; ++i) {
+        double* o = counts + ((size_t)(n0 + i) * total + p0) * T;
+        const double* src = hbuf.data() + (size_t)i * T * h->n_pad;
+        for (int64_t p = 0; p < h->n_patterns; ++p)
+          for (int k = 0; k < T; ++k) o[p * T + k] = src[(size_t)k * h->n_pad + p];
+      }
+    }
+    if (blocks) {
+      hbuf.resize((size_t)cn * T * nB);
+      HIPCHK(h, hipMemcpy(hbuf.data(), d_out, hbuf.size() * sizeof(double), hipMemcpyDeviceToHost));
+      for (int i = 0; i < cn; ++i)
+        for (int k = 0; k < T; ++k)
+          std::copy(hbuf.begin() + ((size_t)i * T + k) * nB, hbuf.begin() + ((size_t)i * T + k + 1) * nB,
+                    blocks + ((size_t)(n0 + i) * T + k) * nB_total + B0);
+    }
+  }
+  return PLK_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -4673,6 +4994,144 @@ int plk_node_posteriors(plk_handle h, int n_nodes, const int32_t* nodes, double*
   }
   // (under a communicator: the rank's own patterns, no collective call)
   return node_posteriors_local(h, n_nodes, nodes, joint, state_post, class_post, best_state, h->n_patterns, 0);
+}
+
+int plk_set_count_types(plk_handle h, int model, int n_types, const double* B) {
+  env_refresh();
+  if (h && !h->shards.empty()) return multi_each(h, [&](plk_handle x) { return plk_set_count_types(x, model, n_types, B); });
+  if (!h || !B || model < 0 || model >= h->n_models) return fail(h, PLK_ERR_ARG, "bad count types (model %d)", model);
+  int rc = map_fix_types(h, n_types);
+  if (rc) return rc;
+  h->count_B[model].assign(B, B + (size_t)n_types * h->S * h->S);
+  h->count_G_dirty[model] = 1;
+  return h->eigen_set[model] ? map_form_G(h, model) : PLK_OK;  // (else: formed by the first request)
+}
+
+int plk_update_count_matrices(plk_handle h, int n, const int32_t* branch, const int32_t* model, const double* t) {
+  env_refresh();
+  if (h && !h->shards.empty()) return multi_each(h, [&](plk_handle x) { return plk_update_count_matrices(x, n, branch, model, t); });
+  if (!h || n < 0 || (n > 0 && (!branch || !t))) return fail(h, PLK_ERR_ARG, "bad count-matrix request");
+  if (n == 0) return PLK_OK;
+  if (!h->rates_set) return fail(h, PLK_ERR_STATE, "plk_set_category_rates must precede plk_update_count_matrices");
+  for (int i = 0; i < n; ++i) {
+    if (branch[i] < 0 || branch[i] >= h->n_nodes) return fail(h, PLK_ERR_ARG, "branch %d out of range", branch[i]);
+    const int m = model ? model[i] : 0;
+    if (m < 0 || m >= h->n_models) return fail(h, PLK_ERR_ARG, "model %d out of range", m);
+    if (!h->eigen_set[m]) return fail(h, PLK_ERR_STATE, "eigen system %d not set", m);
+    if (!h->count_T || h->count_B[m].empty())
+      return fail(h, PLK_ERR_STATE, "model %d has no substitution types (plk_set_count_types)", m);
+    if (!(t[i] >= 0.0)) return fail(h, PLK_ERR_ARG, "branch length %g not >= 0", t[i]);
+  }
+  hipSetDevice(h->device);
+  int rc;
+  for (int i = 0; i < n; ++i) {
+    const int m = model ? model[i] : 0;
+    if (h->count_G_dirty[m] && (rc = map_form_G(h, m))) return rc;
+  }
+  const int S = h->S, C = h->C;
+  const size_t off_b = (size_t)n * sizeof(double), off_m = off_b + (size_t)n * sizeof(int32_t);
+  std::vector<char> req(off_m + (size_t)n * sizeof(int32_t));
+  std::memcpy(req.data(), t, n * sizeof(double));
+  std::memcpy(req.data() + off_b, branch, n * sizeof(int32_t));
+  if (model) std::memcpy(req.data() + off_m, model, n * sizeof(int32_t));
+  if ((rc = ensure_cap(h, (void**)&h->d_mapreq, &h->d_mapreq_cap, req.size()))) return rc;
+  HIPCHK(h, hipMemcpyAsync(h->d_mapreq, req.data(), req.size(), hipMemcpyHostToDevice, h->stream));
+  CountMatArgs a;
+  a.t = reinterpret_cast<const double*>(h->d_mapreq);
+  a.branch = reinterpret_cast<const int32_t*>(h->d_mapreq + off_b);
+  a.model = model ? reinterpret_cast<const int32_t*>(h->d_mapreq + off_m) : nullptr;
+  a.rates = h->rates;
+  a.V = h->V;
+  a.Vinv = h->Vinv;
+  a.lambda = h->lambda;
+  a.G = h->count_G;
+  a.W = h->wmats;
+  a.S = S;
+  a.C = C;
+  a.T = h->count_T;
+  a.n_req = n;
+  EventPair ev;
+  if (h->timing & PLK_TIME_PMAT) {
+    ev = get_events(h, 1);
+    hipEventRecord(ev.a, h->stream);
+  }
+  if (S <= 4) {
+    const unsigned g4 = (unsigned)((n * C * S + 63) / 64);
+    switch (S) {
+      case 2: count_matrix4_kernel<2><<<g4, 64, 0, h->stream>>>(a); break;
+      case 3: count_matrix4_kernel<3><<<g4, 64, 0, h->stream>>>(a); break;
+      case 4: count_matrix4_kernel<4><<<g4, 64, 0, h->stream>>>(a); break;
+    }
+  } else {
+    count_matrix_kernel<<<dim3(n, C), 256, 2 * (size_t)S * S * sizeof(double), h->stream>>>(a);
+  }
+  HIPCHK(h, hipGetLastError());
+  if (h->timing & PLK_TIME_PMAT) {
+    hipEventRecord(ev.b, h->stream);
+    h->events.push_back(ev);
+  }
+  HIPCHK(h, hipStreamSynchronize(h->stream));  // req is read by the copy
+  for (int i = 0; i < n; ++i) h->wmat_valid[branch[i]] = 1;
+  return PLK_OK;
+}
+
+int plk_set_count_matrix(plk_handle h, int branch, int n_types, const double* W) {
+  env_refresh();
+  if (h && !h->shards.empty()) return multi_each(h, [&](plk_handle x) { return plk_set_count_matrix(x, branch, n_types, W); });
+  if (!h || !W || branch < 0 || branch >= h->n_nodes) return fail(h, PLK_ERR_ARG, "bad branch %d", branch);
+  int rc = map_fix_types(h, n_types);
+  if (rc) return rc;
+  hipSetDevice(h->device);
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  const size_t n = (size_t)n_types * h->C * h->S * h->S;
+  HIPCHK(h, hipMemcpy(h->wmats + (size_t)branch * n, W, n * sizeof(double), hipMemcpyHostToDevice));
+  h->wmat_valid[branch] = 1;
+  return PLK_OK;
+}
+
+int plk_get_count_matrix(plk_handle h, int branch, double* W) {
+  env_refresh();
+  if (h && !h->shards.empty()) return multi_forward(h, plk_get_count_matrix(h->shards[0], branch, W));
+  if (!h || !W || branch < 0 || branch >= h->n_nodes) return fail(h, PLK_ERR_ARG, "bad branch %d", branch);
+  if (!h->count_T || !h->wmat_valid[branch]) return fail(h, PLK_ERR_STATE, "branch %d has no count matrix", branch);
+  hipSetDevice(h->device);
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  const size_t n = (size_t)h->count_T * h->C * h->S * h->S;
+  HIPCHK(h, hipMemcpy(W, h->wmats + (size_t)branch * n, n * sizeof(double), hipMemcpyDeviceToHost));
+  return PLK_OK;
+}
+
+int plk_branch_counts(plk_handle h, int n_branches, const int32_t* branches, double* counts, double* totals) {
+  env_refresh();
+  if (!h) return fail(h, PLK_ERR_ARG, "null handle");
+  if (n_branches <= 0 || !branches) return fail(h, PLK_ERR_ARG, "bad branch list (%d branches)", n_branches);
+  if (!counts && !totals) return fail(h, PLK_ERR_ARG, "no output requested");
+  const bool multi = !h->shards.empty();
+  const int T = multi ? h->shards[0]->count_T : h->count_T;
+  // block sums of every shard at their global block index, added in that order below: the
+  // root reduction's rule, so the totals do not depend on the sharding
+  const int64_t nB = (h->n_patterns + kRootBlock - 1) / kRootBlock;
+  std::vector<double> blocks;
+  if (totals) blocks.assign((size_t)n_branches * std::max(T, 1) * nB, 0.0);
+  double* bp = totals ? blocks.data() : nullptr;
+  int rc;
+  if (multi) {
+    // every shard fills its pattern range of the caller's array and its blocks
+    rc = multi_slices(h, [&](plk_handle x, int64_t a) {
+      return branch_counts_local(x, n_branches, branches, counts, bp, h->n_patterns, a, nB, a / kRootBlock);
+    });
+  } else {
+    // (under a communicator: the rank's own patterns and totals, no collective call)
+    rc = branch_counts_local(h, n_branches, branches, counts, bp, h->n_patterns, 0, nB, 0);
+  }
+  if (rc) return rc;
+  if (totals)
+    for (size_t r = 0; r < (size_t)n_branches * T; ++r) {
+      double s = 0.0;
+      for (int64_t B = 0; B < nB; ++B) s += blocks[r * nB + B];
+      totals[r] = s;
+    }
+  return PLK_OK;
 }
 
 const char* plk_kernel_path(plk_handle h) {

@@ -24,6 +24,14 @@ struct plk_handle_s;
 
 namespace bpp {
 
+class SubstitutionCount;
+
+// Substitution types an engine handle was fixed to (0: none yet), kept beside the likelihood
+// classes in src/Mapping.cpp so that their layout is what programs compiled against the
+// earlier headers expect; the entry goes when the handle is destroyed.
+size_t& engineCountTypes(const plk_handle_s* engine);
+void forgetEngineCountTypes(const plk_handle_s* engine);
+
 class TreeLikelihood : public AbstractParametrizable {
  public:
   virtual ~TreeLikelihood() {}
@@ -241,6 +249,16 @@ class AbstractPlkTreeLikelihood : public virtual TreeLikelihood {
   };
   NodePosteriors computeNodePosteriors(const std::vector<int>& nodeIds, bool joint, bool states, bool classes,
                                        bool best) const;
+  // Substitution mapping (Mapping/SubstitutionMappingTools.h): the posterior expected number of
+  // substitutions of each type of `count`'s register on the branches above `nodeIds`, per
+  // distinct pattern, flat [branch][pattern][type] (plk_branch_counts).  Needs a
+  // double-recursive likelihood.  A DecompositionSubstitutionCount on this likelihood's own
+  // model has its count matrices formed on the device (plk_set_count_types +
+  // plk_update_count_matrices); any other count is asked for N(r_c t) on the host and
+  // N o P goes up with plk_set_count_matrix.  The engine holds one type count per handle: a
+  // register with fewer types than an earlier one is padded with empty types, one with more
+  // needs another likelihood object.
+  std::vector<double> computeBranchCounts(const std::vector<int>& nodeIds, SubstitutionCount& count) const;
   bool isLeafNode(int nodeId) const { return tree_->getNode(nodeId)->isLeaf(); }
   std::vector<int> getInnerNodesId() const;
   // a leaf's init values per distinct pattern, [pattern][state]

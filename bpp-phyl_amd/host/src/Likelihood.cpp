@@ -64,7 +64,10 @@ AbstractPlkTreeLikelihood::AbstractPlkTreeLikelihood(const Tree& tree, DiscreteD
 }
 
 AbstractPlkTreeLikelihood::~AbstractPlkTreeLikelihood() {
-  if (engine_) plk_destroy(engine_);
+  if (engine_) {
+    forgetEngineCountTypes(engine_);
+    plk_destroy(engine_);
+  }
   delete tree_;
 }
 
@@ -167,6 +170,7 @@ void AbstractPlkTreeLikelihood::setDataImpl(const SiteContainer& sites, const Al
 
 void AbstractPlkTreeLikelihood::createEngine(size_t nModels, bool nonNegGuard) {
   if (engine_) {
+    forgetEngineCountTypes(engine_);
     plk_destroy(engine_);
     engine_ = nullptr;
   }

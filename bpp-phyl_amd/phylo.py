@@ -447,6 +447,28 @@ def lg08() -> Model:
     return Model("LG08", 20, Q, pi, V, Vinv, lam)
 
 
+# Substitution registers (Mapping/SubstitutionRegister.h): the B matrices of
+# plk_set_count_types, [T, S, S] -- B_k[x][y] = Q[x][y] where x -> y is of type k, else 0
+# (DecompositionSubstitutionCount::fillBMatrices_).
+
+def total_register(Q: np.ndarray) -> np.ndarray:
+    """TotalSubstitutionRegister: every change x != y in one type (T = 1)."""
+    B = np.array(Q, dtype=np.float64)
+    np.fill_diagonal(B, 0.0)
+    return B[None]
+
+
+def comprehensive_register(Q: np.ndarray) -> np.ndarray:
+    """ComprehensiveSubstitutionRegister: one type per ordered pair x != y, numbered row by
+    row as the reference does (T = S (S - 1); the engine takes T <= 16, i.e. DNA)."""
+    S = Q.shape[0]
+    pairs = [(x, y) for x in range(S) for y in range(S) if x != y]
+    B = np.zeros((len(pairs), S, S))
+    for k, (x, y) in enumerate(pairs):
+        B[k, x, y] = Q[x, y]
+    return B
+
+
 STOP_CODONS = [i for i, a in enumerate(_STD_CODE_AA) if a == "*"]
 
 

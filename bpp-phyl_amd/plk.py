@@ -40,7 +40,8 @@ EXPORTS = [
     "plk_comm_init", "plk_get_dpmatrix", "plk_root_pair_derivatives", "plk_get_fanout",
     "plk_root_underflow", "plk_exchange_stride", "plk_exchange_pack", "plk_exchange_reduce",
     "plk_exchange_rank_sums", "plk_clock_records", "plk_clock_waves", "plk_clock_wave_tails",
-    "plk_node_posteriors",
+    "plk_node_posteriors", "plk_set_count_types", "plk_update_count_matrices", "plk_set_count_matrix",
+    "plk_get_count_matrix", "plk_branch_counts",
 ]
 
 
@@ -130,6 +131,11 @@ def load(path: str = LIB_PATH) -> ct.CDLL:
         "plk_root_pair_derivatives": ([ct.c_void_p, ct.c_int, ct.c_int, ct.c_double, ct.c_double, dp, dp], ct.c_int),
         "plk_all_branch_derivatives": ([ct.c_void_p, dp, dp], ct.c_int),
         "plk_node_posteriors": ([ct.c_void_p, ct.c_int, ip, dp, dp, dp, P(ct.c_uint8)], ct.c_int),
+        "plk_set_count_types": ([ct.c_void_p, ct.c_int, ct.c_int, dp], ct.c_int),
+        "plk_update_count_matrices": ([ct.c_void_p, ct.c_int, ip, ip, dp], ct.c_int),
+        "plk_set_count_matrix": ([ct.c_void_p, ct.c_int, ct.c_int, dp], ct.c_int),
+        "plk_get_count_matrix": ([ct.c_void_p, ct.c_int, dp], ct.c_int),
+        "plk_branch_counts": ([ct.c_void_p, ct.c_int, ip, dp, dp], ct.c_int),
         "plk_kernel_path": ([ct.c_void_p], ct.c_char_p),
         "plk_compressed_work": ([ct.c_void_p, P(ct.c_int64)], ct.c_int),
         "plk_evaluate": ([ct.c_void_p, ct.c_int, ip, ip, dp, P(plk_op), ct.c_int, ct.c_int, dp, dp], ct.c_int),
@@ -251,6 +257,7 @@ class Engine:
         self.lib = load()
         self.h = ct.c_void_p()
         self.S, self.C, self.P = n_states, n_classes, n_patterns
+        self.T = 0  # substitution types (set_count_types / set_count_matrix)
         self.n_tips, self.n_internal = n_tips, n_internal
         self._ops_cache = None
         self._eval_cache = None
@@ -478,6 +485,53 @@ class Engine:
             _d(out["joint"]) if joint else None, _d(out["states"]) if states else None,
             _d(out["classes"]) if classes else None,
             out["best"].ctypes.data_as(ct.POINTER(ct.c_uint8)) if best else None))
+        return out
+
+    def set_count_types(self, model: int, B: np.ndarray):
+        """plk_set_count_types: the substitution types of `model`, B [T, S, S] (phylo.total_register,
+        phylo.comprehensive_register).  T is fixed per engine by the first call."""
+        b = np.ascontiguousarray(B, dtype=np.float64)
+        assert b.ndim == 3 and b.shape[1:] == (self.S, self.S)
+        self._chk(self.lib.plk_set_count_types(self.h, model, b.shape[0], _d(b)))
+        self.T = b.shape[0]
+
+    def update_count_matrices(self, branches: np.ndarray, t: np.ndarray, models: Optional[np.ndarray] = None):
+        """plk_update_count_matrices: W^k of the listed branches from the eigen systems."""
+        b = np.ascontiguousarray(branches, dtype=np.int32)
+        tt = np.ascontiguousarray(t, dtype=np.float64)
+        mp = None
+        if models is not None:
+            m = np.ascontiguousarray(models, dtype=np.int32)
+            mp = m.ctypes.data_as(ct.POINTER(ct.c_int32))
+        self._chk(self.lib.plk_update_count_matrices(self.h, len(b), b.ctypes.data_as(ct.POINTER(ct.c_int32)), mp,
+                                                     _d(tt)))
+
+    def set_count_matrix(self, branch: int, W: np.ndarray):
+        """plk_set_count_matrix: host-computed W [T, C, S, S] (counts already times P)."""
+        w = np.ascontiguousarray(W, dtype=np.float64)
+        assert w.ndim == 4 and w.shape[1:] == (self.C, self.S, self.S)
+        self._chk(self.lib.plk_set_count_matrix(self.h, branch, w.shape[0], _d(w)))
+        self.T = w.shape[0]
+
+    def get_count_matrix(self, branch: int) -> np.ndarray:
+        out = np.empty((max(self.T, 1), self.C, self.S, self.S))
+        self._chk(self.lib.plk_get_count_matrix(self.h, branch, _d(out)))
+        return out
+
+    def branch_counts(self, branches, counts: bool = True, totals: bool = True) -> dict:
+        """plk_branch_counts for the branches (child node indices, tips included) of the last
+        traversal: a dict with "counts" [branch, pattern, type], the posterior expected number
+        of substitutions, and "totals" [branch, type], their pattern-weighted sums."""
+        br = np.ascontiguousarray(branches, dtype=np.int32).ravel()
+        n, T = len(br), max(self.T, 1)
+        out = {}
+        if counts:
+            out["counts"] = np.empty((n, self.P, T))
+        if totals:
+            out["totals"] = np.empty((n, T))
+        self._chk(self.lib.plk_branch_counts(
+            self.h, n, br.ctypes.data_as(ct.POINTER(ct.c_int32)),
+            _d(out["counts"]) if counts else None, _d(out["totals"]) if totals else None))
         return out
 
     def set_timing(self, on: bool):

@@ -342,6 +342,68 @@ int plk_node_posteriors(plk_handle h, int n_nodes, const int32_t* nodes,
                         double* class_post /* n_nodes x n_patterns x C, or NULL */,
                         uint8_t* best_state /* n_nodes x n_patterns, or NULL */);
 
+/* Probabilistic substitution mapping: the posterior expected number of substitutions of each
+ * type, on each branch, at each pattern.  A type k (1..T) of a model is a matrix B_k with zero
+ * diagonal: B_k[x][y] = Q[x][y] (times an optional weight) where the register puts x -> y in
+ * type k, 0 elsewhere (DecompositionSubstitutionCount::fillBMatrices_).  With tau = r_c t_v and
+ * the real eigen system (V, Vinv, lambda) of plk_set_eigen,
+ *   G_k = Vinv B_k V,   J[i][j] = int_0^tau exp(lambda_i s) exp(lambda_j (tau - s)) ds,
+ *   W^k_{v,c} = V (J o G_k) Vinv = int_0^tau e^{Qs} B_k e^{Q(tau-s)} ds     (o: elementwise),
+ * W^k[x][y] = E[count of type k, end state y | start state x], the reference's
+ * getAllNumbersOfSubstitutions(tau, k)[x][y] * P(tau)[x][y].  Per branch v (a child node index,
+ * tips included), pattern and type, with u = U_v (pi folded in as in plk_node_posteriors),
+ *   l   = sum_c p_c sum_xy u[c][x] P_v[c][x][y]   L_v[c][y],
+ *   n_k = sum_c p_c sum_xy u[c][x] W^k_{v,c}[x][y] L_v[c][y],      count[v][p][k] = n_k / l.
+ * Scale counts multiply n_k and l alike and are never read.
+ * Replaces SubstitutionMappingTools::computeSubstitutionVectors (Mapping/
+ * SubstitutionMappingTools.cpp:63-372) over DecompositionSubstitutionCount / DecompositionMethods
+ * (Mapping/DecompositionMethods.cpp:88-165).  Deviations:
+ *   - J is formed as tau exp(max(lambda_i, lambda_j) tau) phi(-|lambda_i - lambda_j| tau),
+ *     phi(z) = expm1(z) / z, phi(0) = 1.  The reference's (e_i - e_j) / (lambda_i - lambda_j)
+ *     with an exact == 0 test (:112-125) cancels catastrophically for nearly equal eigenvalues,
+ *     which is what a numeric eigensolver returns for K80- / HKY-like models.
+ *   - An entry of W that rounding leaves below 0 counts as 0.  The reference zeroes negative,
+ *     infinite and NaN quotients N = W / P (DecompositionSubstitutionCount.cpp:100-114); where
+ *     P > 0 the two agree.
+ *   - A pattern whose l is not a positive finite number (an unscaled underflow) gets counts 0
+ *     and no error, as the posteriors do.
+ *   - Real eigen systems only.
+ *
+ * plk_set_count_types: T types for model `model`; B is T x S x S.  T is 1..16 and is fixed per
+ * handle by the first call of plk_set_count_types or plk_set_count_matrix: later calls with
+ * another T are PLK_ERR_ARG.  Forms G_k (again after a later plk_set_eigen of the model). */
+int plk_set_count_types(plk_handle h, int model, int n_types, const double* B);
+
+/* As plk_update_pmatrices: W^k_{branch,c} for every listed branch, class and type, from the
+ * eigen system.  t = 0 gives W = 0.  PLK_ERR_STATE if the model has no types.  Count matrices
+ * are no input of L or U: the preorder pass is not run again because of them. */
+int plk_update_count_matrices(plk_handle h, int n, const int32_t* branch, const int32_t* model, const double* t);
+
+/* Host-computed counts (naive, Laplace, uniformisation: N o P, already times P), as
+ * plk_set_pmatrix; plk_get_count_matrix reads a branch's matrices back.  W lives on the device
+ * as [n_nodes][T][C][S][S], allocated by the first count-matrix call (PLK_ERR_OOM). */
+int plk_set_count_matrix(plk_handle h, int branch, int n_types, const double* W /* T x C x S x S */);
+int plk_get_count_matrix(plk_handle h, int branch, double* W /* T x C x S x S */);
+
+/* counts[b][p][k] for the listed branches of the last plk_update_partials tree, and
+ * totals[b][k] = sum_p w_p counts[b][p][k], summed per plk_block_size() patterns on the device
+ * and over the blocks in pattern order on the host (the root reduction's rule, so the value does
+ * not depend on sharding).  Either output may be NULL (not both); without `counts` no
+ * per-pattern row is written.  Preconditions and error codes follow plk_all_branch_derivatives
+ * and plk_node_posteriors: PLK_ERR_STATE without PLK_FLAG_DOUBLE_RECURSIVE, before a traversal,
+ * without dP / d2P, or for a branch without a count matrix; PLK_ERR_UNSUPPORTED with
+ * PLK_FLAG_SUBTREE_PATTERNS; PLK_ERR_ARG for the root, an index out of range, a node outside the
+ * current tree, n_branches <= 0 or both outputs NULL.  The preorder pass runs only if a P(t),
+ * partial, tip code, pi or rate has changed since the last one; the upper vectors of requested
+ * tip branches, which that pass does not keep, are formed once per such change.  A multi-device
+ * handle fills `counts` shard by shard and adds block totals in global block order (both outputs
+ * bitwise the single-device ones); under a communicator a rank returns its own patterns and
+ * totals, with no collective call.  Device staging of `counts` is bounded (256 MiB): longer
+ * branch lists run in chunks. */
+int plk_branch_counts(plk_handle h, int n_branches, const int32_t* branches,
+                      double* counts /* n_branches x n_patterns x T, or NULL */,
+                      double* totals /* n_branches x T, or NULL */);
+
 /* Instrumentation: HIP-event timing on the handle's stream of the kernels selected
  * by the mask given to plk_set_timing (0 = off).  Each timed launch adds an event
  * pair to the stream, so time only what is needed. */
