@@ -542,6 +542,34 @@ EventPair get_events(plk_handle h, int kind) {
   return e;
 }
 
+// One timed bracket on the handle's stream.  When h->timing has `mask` (and `on` holds) it takes
+// an event pair and records `a`; stop() records `b`, queues the pair for collect_events and says
+// whether the bracket was timed, so the call sites that count timed launches count there.  A
+// bracket that goes out of scope without stop() -- an error return in between -- hands its pair
+// back to the pool.
+struct TimedSpan {
+  plk_handle h;
+  EventPair ev;
+  bool open;
+  TimedSpan(plk_handle h_, unsigned mask, int kind, bool on = true) : h(h_), open(on && (h_->timing & mask)) {
+    if (!open) return;
+    ev = get_events(h, kind);
+    hipEventRecord(ev.a, h->stream);
+  }
+  TimedSpan(const TimedSpan&) = delete;
+  TimedSpan& operator=(const TimedSpan&) = delete;
+  bool stop() {
+    if (!open) return false;
+    hipEventRecord(ev.b, h->stream);
+    h->events.push_back(ev);
+    open = false;
+    return true;
+  }
+  ~TimedSpan() {
+    if (open) h->event_pool.push_back(ev);
+  }
+};
+
 int collect_events(plk_handle h) {
   if (h->events.empty()) return PLK_OK;
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1520,11 +1548,7 @@ int plk_update_pmatrices(plk_handle h, int n, const int32_t* branch, const int32
   a.tipP = h->tipP;
   a.n_tips = h->n_tips;
   a.n_codes = h->n_codes;
-  EventPair ev;
-  if (h->timing & PLK_TIME_PMAT) {
-    ev = get_events(h, 1);
-    hipEventRecord(ev.a, h->stream);
-  }
+  TimedSpan span(h, PLK_TIME_PMAT, 1);
   const size_t lds = (size_t)(h->S + (tips_fused ? 3 : 2) * S2) * sizeof(double);
   // pmat64s_kernel and pmat_kernel also write the transposed copy the matrix-core kernels
   // read (allocated by the first transposed-P use), so an evaluation needs no transpose launch
@@ -1579,10 +1603,7 @@ int plk_update_pmatrices(plk_handle h, int n, const int32_t* branch, const int32
     else
       HIPCHK(h, hipEventRecord(h->req_done, h->stream));
   }
-  if (h->timing & PLK_TIME_PMAT) {
-    hipEventRecord(ev.b, h->stream);
-    h->events.push_back(ev);
-  }
+  span.stop();
   if (deriv_mask & PLK_DERIV_P) {
     for (int i = 0; i < n; ++i) {
       h->pmat_valid[branch[i]] = 1;
@@ -2067,7 +2088,11 @@ void launch_treeM(plk_handle h, const TreeArgs& a, dim3 grid, size_t lds) {
   }
 }
 
-int update_tree4(plk_handle h, const plk_op* ops, int n_ops) {
+// update_tree4 in stages, in the order they run.
+
+// Program cache: the fragment program of these ops as the handle is set up now, built again
+// only when one of them changed; a cached program replays what it leaves materialised.
+int tree4_program(plk_handle h, const plk_op* ops, int n_ops) {
   const bool materialize = !(h->flags & PLK_FLAG_LNL_ONLY);
   const bool reduce = h->pi_set && h->rates_set;
   const bool same = h->prog_ops.size() == (size_t)n_ops && h->prog_materialize == materialize &&
@@ -2075,46 +2100,28 @@ int update_tree4(plk_handle h, const plk_op* ops, int n_ops) {
                     h->prog_jitm == jit_treeM(h) &&
                     (!h->prog_jit || h->prog_tmax == jit_tip_cap(h)) &&
                     std::memcmp(h->prog_ops.data(), ops, n_ops * sizeof(plk_op)) == 0;
-  if (!same) {
-    int rc = build_tree4_program(h, ops, n_ops, materialize, reduce);
-    if (rc) return rc;
-  } else {
-    for (size_t i = 0; i < h->prog_mat_after.size(); ++i)
-      if (h->prog_mat_after[i] >= 0) h->materialized[i] = (char)h->prog_mat_after[i];
-  }
-  if (!h->table_set) return fail(h, PLK_ERR_STATE, "code table not set (plk_set_code_table)");
-  const FusedKind kind = fused_kind(h);
-  if (kind != FK_TREE4 || h->prog_jit) {
-    int rc = refresh_tip_tables(h);
-    if (rc) return rc;
-  }
-  if (kind == FK_TREEM) {
-    int rc = ensure_pmatsT(h);
-    if (rc) return rc;
-    EventPair tev;
-    const bool timed = (h->timing & PLK_TIME_TABLES) && !h->cherry3.empty();
-    if (timed) {
-      tev = get_events(h, 3);
-      hipEventRecord(tev.a, h->stream);
-    }
-    rc = build_cherry_tables(h);
-    if (rc) return rc;
-    if (timed) {
-      hipEventRecord(tev.b, h->stream);
-      h->events.push_back(tev);
-      h->n_table_launches++;
-    }
-  }
-  TreeArgs a;
-  a.uflow = h->prog_root >= 0 ? uflow_arm(h) : nullptr;
-  a.cherry = h->d_cherry;
-  a.prog = h->d_prog;
+  if (!same) return build_tree4_program(h, ops, n_ops, materialize, reduce);
+  for (size_t i = 0; i < h->prog_mat_after.size(); ++i)
+    if (h->prog_mat_after[i] >= 0) h->materialized[i] = (char)h->prog_mat_after[i];
+  return PLK_OK;
+}
+
+// treeM: transposed P(t) and the cherry contribution tables, timed as table launches
+int treeM_tables(plk_handle h) {
+  int rc = ensure_pmatsT(h);
+  if (rc) return rc;
+  TimedSpan span(h, PLK_TIME_TABLES, 3, !h->cherry3.empty());
+  rc = build_cherry_tables(h);
+  if (rc) return rc;
+  if (span.stop()) h->n_table_launches++;
+  return PLK_OK;
+}
+
+// The fields TreeArgs, JArgs and JMArgs share, from the handle
+template <class Args>
+void fill_common_args(plk_handle h, int32_t* uflow, Args& a) {
   a.partials = h->partials;
   a.scale = h->scale;
-  a.codes = h->codes;
-  a.pmats = h->pmats;
-  a.init = h->code_table;
-  a.tipP = h->tipP;
   a.weights = h->weights;
   a.pi = h->pi;
   a.probs = h->probs;
@@ -2123,369 +2130,425 @@ int update_tree4(plk_handle h, const plk_op* ops, int n_ops) {
   a.slot_stride = h->slot_stride;
   a.n_pad = h->n_pad;
   a.n_patterns = h->n_patterns;
-  a.n_codes = h->n_codes;
   a.guard = (h->flags & PLK_FLAG_NONNEG_GUARD) ? 1 : 0;
+  a.uflow = uflow;
+}
+
+// The interpreters' argument block (frag_start is set per tier); returns tree4_kernel's LDS bytes
+size_t tree_args(plk_handle h, TreeArgs& a) {
+  fill_common_args(h, h->prog_root >= 0 ? uflow_arm(h) : nullptr, a);
+  a.cherry = h->d_cherry;
+  a.prog = h->d_prog;
+  a.codes = h->codes;
+  a.pmats = h->pmats;
+  a.init = h->code_table;
+  a.tipP = h->tipP;
+  a.n_codes = h->n_codes;
   a.n_tips = h->n_tips;
   a.C = h->C;
   a.stage_codes = (h->n_tips * 64 <= 64 * 1024) ? 1 : 0;
-  const size_t lds = (size_t)((h->n_codes * 4 + 1) & ~1) * sizeof(double) + kTreeMaxWaves * 64 * sizeof(double) +
-                     (a.stage_codes ? (size_t)h->n_tips * 64 : 0);
   a.n_frags = h->prog_nf;
   a.bmask = -1;
   a.cherry_pairs = 1;
   a.n_cherry_staged = 0;
+  return (size_t)((h->n_codes * 4 + 1) & ~1) * sizeof(double) + kTreeMaxWaves * 64 * sizeof(double) +
+         (a.stage_codes ? (size_t)h->n_tips * 64 : 0);
+}
+
+// treeM: LDS table buffers and the code staging decision; sets a.buf_doubles, a.stage_codes and
+// the kernel's LDS bytes
+int treeM_staging(plk_handle h, TreeArgs& a, size_t& lds_m) {
+  a.buf_doubles = std::max(h->C * h->S * h->S, h->C * h->n_codes * h->S);
+  a.buf_doubles = (a.buf_doubles + 1) & ~1;
+  const int threads = 64 * treeM_groups(h) * (h->S == 64 ? 1 : h->C);
+  const int pf = h->S == 64 ? treeM_pf<64>() : treeM_pf<20>();
+  if (!h->prog_jitm && !treeM_direct(h) && a.buf_doubles > pf * threads)
+    return fail(h, PLK_ERR_UNSUPPORTED, "fused MFMA tables (%d doubles) exceed the staging registers",
+                a.buf_doubles);
+  a.buf_doubles = std::max(a.buf_doubles, (pf - 1) * threads);  // unconditional stores stay inside
+  if (treeM_direct(h)) a.buf_doubles = 0;  // tables read from L1/L2: LDS holds the codes only
+  lds_m = 2 * (size_t)a.buf_doubles * sizeof(double);
+  a.stage_codes = (lds_m + (size_t)h->n_tips * 64 <= 76 * 1024) ? 1 : 0;  // two workgroups per CU
+  // a program whose tips all sit in cherry tables (balanced trees) has no T_TIP event:
+  // staging every tip's codes would only cost each workgroup a load of n_tips x 64 B
+  if (std::none_of(h->prog_host.begin(), h->prog_host.end(), [](const TInstr& w) { return w.op == T_TIP; }))
+    a.stage_codes = 0;
+  if (a.stage_codes) lds_m += (size_t)h->n_tips * 64;
+  return PLK_OK;
+}
+
+// The table plan of the generated tree4 kernel for U codes: rebuilt when the program (which
+// clears jit_plan_valid), the codes in use or a table budget changed.  A new plan needs a new
+// kernel and new unit codes.
+void jit4_ensure_plan(plk_handle h, int U, bool scale) {
+  // cherries read one product table (plk_jit.hpp: JitUnit) while a fragment's tables stay
+  // within PLK_JIT_PAIR_KB (0: no pairs)
+  const int budget = tune_int("JIT_PAIR_KB", 64, 0, 150) * 1024 / (int)sizeof(double);
+  // One class per workgroup with quad units (plk_jit.hpp JitUnit, JitShape::cls): tables of
+  // one class, so a fragment's cherries fit as 4-tip subtree tables -- for one class per wave,
+  // no rescaling, lnL only (quads are never stored) and at most 4 codes in use (U^4 <= 256).
+  // PLK_TUNE JIT_QUAD_KB bounds the tables (0: off); the plan is rebuilt as usual when it
+  // gets no quad.
+  const bool cls_ok = !h->prog_ciw && !scale && (h->flags & PLK_FLAG_LNL_ONLY) && U <= 4;
+  const int qb = cls_ok ? tune_int("JIT_QUAD_KB", 136, 0, 150) * 1024 / (int)sizeof(double) : 0;
+  if (h->jit_plan_valid && h->jit_plan_U == U && h->jit_plan_budget == budget && h->jit_plan_qb == qb) return;
+  h->jit_plan_cls = false;
+  if (qb > 0) {
+    h->jit_plan = jit_plan(h->prog_host, h->frag_starts_host, h->C, U, std::max(qb, budget), scale, true, qb);
+    for (const auto& un : h->jit_plan.units)
+      for (const JitUnit& u : un) h->jit_plan_cls |= u.tc >= 0;
+  }
+  if (!h->jit_plan_cls) h->jit_plan = jit_plan(h->prog_host, h->frag_starts_host, h->C, U, budget, scale);
+  h->jit_plan_valid = true;
+  h->jit_plan_U = U;
+  h->jit_plan_budget = budget;
+  h->jit_plan_qb = qb;
+  h->jit_fn = nullptr;
+  h->ucodes_valid = false;
+}
+
+// The shape of the generated tree4 kernel (4 states, one class per wave or every class in the
+// wave; PLK_JIT=0 keeps the interpreter, e.g. for A/B measurements): every field, from the
+// handle, the tunes and the current plan.
+int jit4_shape(plk_handle h, JitShape& sh) {
+  sh.C = h->C;
+  sh.CW = h->prog_ciw ? h->C : 1;
+  sh.pin = true;  // accumulator pinning: cfg2 0.244 -> 0.241, cfg5 1.04 -> 0.93 ms
+  sh.U = h->n_codes;
+  sh.scale = (h->flags & PLK_FLAG_SCALING) != 0;
+  jit4_ensure_plan(h, sh.U, sh.scale);
+  sh.cls = h->jit_plan_cls;
+  sh.NT = h->jit_plan.NU;
+  sh.TD = h->jit_plan.tab_doubles;
+  sh.QT = h->jit_plan.quad_tmp;
+  sh.soa = tune_int("JIT_SOA", 1, 0, 1) != 0;
+  // direct codes where a fragment has at most 16 units (cfg2, 0.099 vs 0.111 ms traversal);
+  // every class in the wave: up to 32 units in two 16-byte words (cfg5 shard traversal
+  // 345-353 vs 367-368 us; PLK_TUNE JIT_DC_CIW=0 keeps the code rows in LDS)
+  sh.dc = sh.cls ? sh.NT <= 16 && tune_int("JIT_DC", 1, 0, 1) != 0
+                 : h->prog_ciw && sh.NT <= 32 && tune_int("JIT_DC_CIW", 1, 0, 1) != 0;
+  sh.dcw = sh.NT <= 16 ? 1 : 2;
+  sh.ps1 = tune_int("JIT_PS1", 0, 0, 1) != 0;
+  // pattern groups per workgroup (they share the staged tables): with per-node rescaling
+  // and one class per wave every node has two workgroup barriers, whose cost grows with
+  // the waves that meet there (cfg5: 1.93 ms at G = 2, 1.16 ms at G = 1), so one group;
+  // every class in the wave (no barriers, ~230 VGPRs, two waves per SIMD): eight, the
+  // whole CU's resident waves in one workgroup that stages the tables once (cfg5 at DM 6
+  // with the tier's fragments side by side: G = 6 / 7 / 8 = 0.48 / 0.43 / 0.39 ms);
+  // otherwise the G with the most resident waves (jit_auto_groups; cfg2 with cherry
+  // tables: G = 3, 0.140 ms, G = 2 0.150, G = 4 0.162)
+  // (before G: the code rows take G x PW).  With direct codes (one class per workgroup, no code
+  // rows in LDS) two patterns per lane: twice the independent work per wave at four waves
+  // per SIMD (cfg2 traversal 0.093 vs 0.099 ms)
+  sh.PW = tune_int("JIT_PW", sh.dc && sh.cls ? 2 : 1, 1, 2);
+  sh.G = tune_int("JIT_G", 0, 0, 16);
+  if (sh.G == 0) {
+    if (sh.cls) {
+      // one class per workgroup: the tables take most of the LDS, so one workgroup per CU
+      // and as many groups as fit (at most 16: 1024 threads)
+      sh.G = 16;
+      while (sh.G > 1 && sh.lds_bytes() > 160 * 1024 - 64) --sh.G;
+    } else {
+      sh.G = h->prog_ciw ? 8 : sh.scale ? 1 : jit_auto_groups(sh);
+    }
+  }
+  sh.G = std::max(1, std::min(sh.G, 1024 / (64 * sh.nw())));  // (a JIT_G past 1024 threads)
+  // wave tasks (direct codes, one wave per pattern group): no barrier in the loop, every wave
+  // walks its own 64 * PW-pattern tasks (plk_jit.hpp; PLK_TUNE JIT_WT=0 is the super-block
+  // schedule with its barrier per super-block, kept for A/B runs)
+  // (on for one class per workgroup, where the barrier wait was 22 % of a wave's loop; the
+  // every-class-in-the-wave kernel waits 1.8 % there and keeps the super-block schedule)
+  sh.wt = sh.wt_ok() && tune_int("JIT_WT", sh.cls ? 1 : 0, 0, 1) != 0;
+  // workgroup task pool (wave tasks only; PLK_TUNE JIT_WP=0 is the static stride, kept for A/B
+  // runs): a workgroup's waves draw its tasks (x, x + gridDim.x, ...) from one LDS counter, so
+  // every workgroup owns floor or ceil of n_tasks / gridDim.x tasks and a wave that ran slowly
+  // takes fewer of them (plk_jit.hpp)
+  sh.wp = sh.wt && tune_int("JIT_WP", sh.cls ? 1 : 0, 0, 1) != 0;
+  // two patterns per lane halve the P(t) reads per FMA but double the registers:
+  // measured slower (cfg2 0.255-0.301 vs 0.241 ms), so opt-in; not with speculation
+  // two-stage pipeline, codes / HBM loads 3 ahead (cfg2 0.274 -> 0.259 ms); with every
+  // class in the wave a ring slot is C x larger, so there two events ahead (cfg5 0.385 ms
+  // at L = 2, 0.391 at L = 1; 1.48 vs 1.04 ms at L = 3 vs 1 before the P(t) stream)
+  sh.L = tune_int("JIT_L", h->prog_ciw ? 2 : 3, 1, 8);
+  sh.RD = tune_int("JIT_RD", 1, 1, 8);  // table rows this many fetchers ahead (<= JIT_L)
+  sh.minw = 0;
+  // speculative no-rescale pass (plk_jit.hpp): a win only where rescaling never
+  // fires; on cfg5 it fires in almost every super-block (1.27 vs 1.14 ms), so opt-in
+  // classes in the wave: next class's P(t) loads overlap this class's FMAs
+  sh.ppipe = true;
+  sh.clk = env_is("PLK_DEBUG_CLOCK", '1') ? 1 : env_is("PLK_DEBUG_CLOCK", '2') ? 2 : env_is("PLK_DEBUG_CLOCK", '3') ? 3 : 0;
+  // PLK_JIT_BLOCKS=1: the root fragment forms the block sums (no wave_sums_to_blocks
+  // launch).  Measured slower (cfg2 traversal 0.125 -> 0.160 ms): the wave that stores a
+  // wave sum must wait for the store and the counter's atomic round trip (~3 us) before
+  // its workgroup's next super-block barrier, in every super-block.  Off; the formal
+  // release/acquire form (an L2 write-back per wave) was slower still (round 1).
+  // (That barrier is what wave tasks take out of the loop -- sh.wt above: a round of the
+  // super-block schedule costs what its slowest wave costs.  The class reduction stays a
+  // launch of its own: its handshake would put the same round trip back into every task.)
+  if (sh.lds_bytes() > 160 * 1024 - 64)  // (less the kernel's static LDS word)
+    return fail(h, PLK_ERR_UNSUPPORTED, "tree kernel needs %zu B of LDS", sh.lds_bytes());
+  return PLK_OK;
+}
+
+// Unit codes of the current plan: one code row per table unit (d_ucodes) and, for a
+// direct-codes shape, their repack as 16-byte words per pattern (d_ucodes_dc)
+int jit4_unit_codes(plk_handle h, const JitShape& sh) {
+  if (!h->ucodes_valid) {
+    std::vector<int4> units;
+    for (const auto& un : h->jit_plan.units)
+      for (const JitUnit& u : un) units.push_back(make_int4(u.ta, u.tb, u.tc, u.td));
+    int rc = ensure_cap(h, (void**)&h->d_ucodes, &h->ucodes_cap, std::max<size_t>(units.size(), 1) * h->n_pad);
+    if (!rc) rc = ensure_cap(h, (void**)&h->d_units, &h->units_cap, std::max<size_t>(units.size(), 1) * sizeof(int4));
+    if (rc) return rc;
+    if (!units.empty()) {
+      HIPCHK(h, hipMemcpyAsync(h->d_units, units.data(), units.size() * sizeof(int4), hipMemcpyHostToDevice,
+                               h->stream));
+      const dim3 ug((unsigned)((h->n_pad / 16 + 255) / 256), (unsigned)units.size());
+      hipLaunchKernelGGL(unit_codes_kernel, ug, dim3(256), 0, h->stream, h->codes, h->n_pad, h->d_units, sh.U,
+                         h->d_ucodes);
+      HIPCHK(h, hipGetLastError());
+      HIPCHK(h, hipStreamSynchronize(h->stream));  // `units` goes out of scope
+    }
+    h->ucodes_valid = true;
+    h->ucodes_dc_valid = false;
+  }
+  if (sh.dc && (!h->ucodes_dc_valid || h->ucodes_dc_w != sh.dcw)) {
+    const int nfr = (int)h->jit_plan.units.size();
+    std::vector<int32_t> us(1, 0);
+    for (const auto& un : h->jit_plan.units) us.push_back(us.back() + (int)un.size());
+    int rc = ensure_cap(h, (void**)&h->d_ucodes_dc, &h->ucodes_dc_cap, (size_t)nfr * h->n_pad * 16 * sh.dcw);
+    if (!rc) rc = ensure_cap(h, (void**)&h->d_units_start, &h->units_start_cap, us.size() * sizeof(int32_t));
+    if (rc) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->d_units_start, us.data(), us.size() * sizeof(int32_t), hipMemcpyHostToDevice,
+                             h->stream));
+    const dim3 dg((unsigned)((h->n_pad + 255) / 256), (unsigned)nfr);
+    hipLaunchKernelGGL(unit_codes_dc_kernel, dg, dim3(256), 0, h->stream, h->d_ucodes, h->n_pad, h->d_units_start,
+                       sh.dcw, reinterpret_cast<uint4*>(h->d_ucodes_dc));
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));  // `us` goes out of scope
+    h->ucodes_dc_valid = true;
+    h->ucodes_dc_w = sh.dcw;
+  }
+  return PLK_OK;
+}
+
+// Compile the generated tree4 kernel when there is none for this plan and shape
+int jit4_compile(plk_handle h, const JitShape& sh) {
+  if (h->jit_fn && sh == h->jit_shape) return PLK_OK;
+  int rc = jit_function(h, jit_tree4_source(h->jit_plan, sh), jit_tree4_name(sh), &h->jit_fn);
+  if (rc) return rc;
+  h->jit_shape = sh;
+  h->jit_resident = 0;
+  return PLK_OK;
+}
+
+// The generated tree4 kernel's argument block for h->jit_shape (dyn and exit_ctr: per launch)
+int jit4_args(plk_handle h, int32_t* uflow, JArgs& ja) {
+  const JitShape& sh = h->jit_shape;
+  fill_common_args(h, uflow, ja);
+  ja.codes = sh.dc ? h->d_ucodes_dc : h->d_ucodes;
+  ja.tipP = h->tipP;
+  ja.n_sblocks = (int32_t)((h->n_pad + 64 * sh.G * sh.PW - 1) / (64 * sh.G * sh.PW));  // last may be ragged
+  ja.n_tasks = (int32_t)((h->n_pad + 64 * sh.PW - 1) / (64 * sh.PW));  // (wave tasks; n_pad is whole tiles)
+  ja.sb_ctr = h->d_sbctr;
+  ja.cls_sum = nullptr;
+  if (sh.cls) {
+    int rc = ensure_cap(h, (void**)&h->d_cls, &h->d_cls_cap, (size_t)h->C * h->n_pad * sizeof(double));
+    if (rc) return rc;
+    ja.cls_sum = h->d_cls;
+  }
+  return PLK_OK;
+}
+
+// The generated treeM kernel: its shape, compiled when there is none for it
+int jitm_compile(plk_handle h) {
+  JitMShape msh;
+  msh.S = h->S;
+  msh.C = h->C;
+  msh.U = h->n_codes;
+  msh.scale = (h->flags & PLK_FLAG_SCALING) != 0;
+  msh.L = tune_int("JITM_L", 1, 1, 4);
+  msh.minw = 2;
+  msh.pd = 1;
+  // contraction issue order: Y-outer with the A operands read ahead and pinned schedule
+  // groups (plk_jitm.hpp CONTRIB; 3.77 -> 3.26 ms on cfg3); the two-stage operand fetch
+  // loads the code 3 events ahead of its row
+  msh.pipe = 2;
+  msh.lc = 3;
+  msh.G = 4;  // 16-pattern waves per workgroup (64 patterns)
+  if (msh.lds_bytes() > 160 * 1024)
+    return fail(h, PLK_ERR_UNSUPPORTED, "jit_treeM needs %zu B of LDS", msh.lds_bytes());
+  if (h->jitm_fn && msh == h->jitm_shape) return PLK_OK;
+  int rc = jit_function(h, jit_treeM4_source(h->prog_host, h->frag_starts_host, msh), "plk_jit_treeM", &h->jitm_fn);
+  if (rc) return rc;
+  h->jitm_shape = msh;
+  return PLK_OK;
+}
+
+void jitm_args(plk_handle h, int32_t* uflow, JMArgs& ma) {
+  const CherryLayout lay(h->C, h->n_codes, h->S, h->n_pad);
+  fill_common_args(h, uflow, ma);
+  ma.codes = h->codes;
+  ma.tipP = h->tipP;
+  ma.cherry = h->d_cherry;
+  ma.pmats = h->pmats;
+  ma.cherry_stride = (int64_t)lay.stride;
+  ma.cherry_table_bytes = (int64_t)lay.table_bytes;
+  ma.cherry_count_bytes = (int64_t)lay.count_bytes;
+}
+
+// PLK_DEBUG_CLOCK: stamp buffer for every workgroup of every tier's launch (grids of
+// launch_jit_tree4: at most jit_resident workgroups per fragment of a tier)
+int grow_clock_stamps(plk_handle h) {
+  size_t need = 0;
+  // (PLK_DEBUG_CLOCK=3: one record per wave; a ragged last workgroup still has all its waves)
+  const size_t per = h->jit_shape.clk == 3 ? (size_t)(h->n_pad / 64 + 16) * h->jit_shape.nw() : (size_t)(h->n_pad / 64);
+  for (const auto& t : h->prog_tiers) need += per * t.size() * (h->jit_shape.cls ? h->C : 1);
+  // The stamps of an evaluation split over several plk_update_partials calls add up: clk_n is
+  // reset where the record is formed (clock_summary), not here.  (Traversals that never reach
+  // a root reduction would grow the buffer without end: past 64 of them the pending stamps are
+  // dropped.)
+  if (h->clk_n > 64 * need) h->clk_n = 0;
+  need += h->clk_n;
+  if (need <= h->clk_cap) return PLK_OK;
+  unsigned long long *nh = nullptr, *nd = nullptr;
+  if (hipHostMalloc((void**)&nh, need * 4 * sizeof(unsigned long long), hipHostMallocMapped) != hipSuccess ||
+      hipHostGetDevicePointer((void**)&nd, nh, 0) != hipSuccess) {
+    if (nh) hipHostFree(nh);
+    return fail(h, PLK_ERR_OOM, "clock stamp buffer");
+  }
+  if (h->h_clk) {
+    if (h->clk_n) {  // the pending traversals' stamps move along, once their kernels have written them
+      if (int rc = stream_wait(h)) {
+        hipHostFree(nh);
+        return rc;
+      }
+      std::memcpy(nh, h->h_clk, h->clk_n * 4 * sizeof(unsigned long long));
+    }
+    hipHostFree(h->h_clk);
+  }
+  h->h_clk = nh;
+  h->d_clk = nd;
+  h->clk_cap = need;
+  return PLK_OK;
+}
+
+// One tier of the generated tree4 kernel: fragments first .. first + nfr - 1 side by side, and
+// the fused class reduction after the root's tier
+int launch_jit_tree4(plk_handle h, JArgs& ja, int first, int nfr) {
+  const JitShape& sh = h->jit_shape;
+  const double* pm = h->pmats;
+  int base = first;
+  const int gz = sh.cls ? h->C : 1;  // one class per workgroup: grid.z = class
+  unsigned long long* clkp = h->d_clk ? h->d_clk + 4 * h->clk_n : nullptr;
+  void* args[] = {&ja, &pm, &base, &clkp};  // (the 4th only exists in a PLK_DEBUG_CLOCK build)
+  // persistent grid: as many workgroups as are resident at once (occupancy query), so
+  // every workgroup stages its tables once and there is no second dispatch round
+  if (h->jit_resident <= 0) {
+    int per_cu = 0, n_cu = 0;
+    HIPCHK(h, hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, h->jit_fn, 64 * sh.nw() * sh.G,
+                                                                 sh.lds_bytes()));
+    HIPCHK(h, hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, h->device));
+    h->jit_resident = std::max(1, per_cu) * std::max(1, n_cu);
+  }
+  // every fragment of the tier at once: the resident workgroups split over the
+  // fragments (each stages its fragment's tables once and walks many super-blocks)
+  // instead of the tier's fragments running one after another with every workgroup
+  // staging tables for a few super-blocks (cfg5 0.49 -> 0.42 ms)
+  int wgs = std::max(1, h->jit_resident / (nfr * gz));
+  // PLK_TUNE JIT_WGS=<n>: at most n persistent workgroups per (fragment, class), so that a
+  // few thousand patterns walk many tasks per workgroup (the dynamic order in small tests)
+  if (const int cap = tune_int("JIT_WGS", 0, 0, 1 << 20)) wgs = std::min(wgs, cap);
+  const unsigned gx = (unsigned)std::min<int64_t>(ja.n_sblocks, wgs);
+  // dynamic super-blocks where a workgroup walks several (a tier of 1-2 per workgroup
+  // gains nothing from them and pays the counter's round trips); wave tasks: where a wave
+  // walks at least three
+  const int64_t units = sh.wt ? ja.n_tasks : ja.n_sblocks, walkers = sh.wt ? (int64_t)gx * sh.G : (int64_t)gx;
+  // (wave tasks take tickets only when asked to, JIT_DYN=1: one ticket per 128-pattern task
+  // is 16 x the atomics on the same counter words, and at cfg2's 1 M patterns -- 7 813
+  // tasks per class over 1 024 waves -- the traversal ran 388 us against 83 with the
+  // super-block schedule, profiles/r07/ab_runs.md; the static stride needs none)
+  // (a task-pool program takes its tickets from LDS: no global counter, no exit ticket)
+  const bool dyn_on = sh.wp ? false : sh.wt ? tune_is("JIT_DYN", '1') : !tune_is("JIT_DYN", '0');
+  ja.dyn = (dyn_on && units >= 3 * walkers) ? 1 : 0;
+  // the launch's counters start at 0; its last workgroup leaves them at 0 (exit ticket)
+  ja.exit_ctr = ja.dyn ? h->d_sbctr + (size_t)h->prog_nf * h->C : nullptr;
+  h->jit_last_gx = (int)gx;
+  if ((int)h->jit_frag_gx.size() < h->prog_nf) h->jit_frag_gx.resize((size_t)h->prog_nf, 0);
+  for (int k = 0; k < nfr; ++k) h->jit_frag_gx[(size_t)(first + k)] = (int)gx;
+  HIPCHK(h, hipModuleLaunchKernel(h->jit_fn, gx, (unsigned)nfr, (unsigned)gz, 64 * sh.nw() * sh.G, 1, 1,
+                                  (unsigned)sh.lds_bytes(),
+                                  h->stream, args, nullptr));
+  if (sh.clk) h->clk_n += (size_t)gx * nfr * gz * (sh.clk == 3 ? (size_t)sh.nw() * sh.G : 1);
+  if (sh.cls && h->prog_root >= 0 && first + nfr == h->prog_nf) {
+    // the classes' root terms meet here: log, site lnL, wave and block sums (the work of
+    // reduce_root and wave_sums_to_blocks), inside the traversal's timing
+    h->fused_cls_blocks = block_target(h);
+    if (int rc = launch_cls_blocks(h, ja.guard, ja.uflow, false)) return rc;
+  }
+  return PLK_OK;
+}
+
+// One tier of the generated treeM kernel
+int launch_jit_treeM(plk_handle h, JMArgs& ma, int first, int nfr) {
+  const JitMShape& msh = h->jitm_shape;
+  int base = first;
+  void* args[] = {&ma, &base};
+  HIPCHK(h, hipModuleLaunchKernel(h->jitm_fn, (unsigned)(h->n_pad / (16 * msh.G)), (unsigned)nfr, 1,
+                                  64 * msh.G, 1, 1, (unsigned)msh.lds_bytes(), h->stream, args, nullptr));
+  return PLK_OK;
+}
+
+int update_tree4(plk_handle h, const plk_op* ops, int n_ops) {
+  if (int rc = tree4_program(h, ops, n_ops)) return rc;
+  if (!h->table_set) return fail(h, PLK_ERR_STATE, "code table not set (plk_set_code_table)");
+  const FusedKind kind = fused_kind(h);
+  if (kind != FK_TREE4 || h->prog_jit) {
+    if (int rc = refresh_tip_tables(h)) return rc;
+  }
+  if (kind == FK_TREEM) {
+    if (int rc = treeM_tables(h)) return rc;
+  }
+  TreeArgs a;
+  const size_t lds = tree_args(h, a);
   size_t lds_m = 0;
   if (kind == FK_TREEM) {
-    a.buf_doubles = std::max(h->C * h->S * h->S, h->C * h->n_codes * h->S);
-    a.buf_doubles = (a.buf_doubles + 1) & ~1;
-    const int threads = 64 * treeM_groups(h) * (h->S == 64 ? 1 : h->C);
-    const int pf = h->S == 64 ? treeM_pf<64>() : treeM_pf<20>();
-    if (!h->prog_jitm && !treeM_direct(h) && a.buf_doubles > pf * threads)
-      return fail(h, PLK_ERR_UNSUPPORTED, "fused MFMA tables (%d doubles) exceed the staging registers",
-                  a.buf_doubles);
-    a.buf_doubles = std::max(a.buf_doubles, (pf - 1) * threads);  // unconditional stores stay inside
-    if (treeM_direct(h)) a.buf_doubles = 0;  // tables read from L1/L2: LDS holds the codes only
-    lds_m = 2 * (size_t)a.buf_doubles * sizeof(double);
-    a.stage_codes = (lds_m + (size_t)h->n_tips * 64 <= 76 * 1024) ? 1 : 0;  // two workgroups per CU
-    // a program whose tips all sit in cherry tables (balanced trees) has no T_TIP event:
-    // staging every tip's codes would only cost each workgroup a load of n_tips x 64 B
-    if (std::none_of(h->prog_host.begin(), h->prog_host.end(), [](const TInstr& w) { return w.op == T_TIP; }))
-      a.stage_codes = 0;
-    if (a.stage_codes) lds_m += (size_t)h->n_tips * 64;
+    if (int rc = treeM_staging(h, a, lds_m)) return rc;
   }
-  // 4 states, one class per wave: the tree-specialised kernel (PLK_JIT=0 keeps the
-  // interpreter, e.g. for A/B measurements)
   const bool jit = h->prog_jit;
   JArgs ja;
-  JitShape sh;
   if (jit) {
-    sh.C = h->C;
-    sh.CW = h->prog_ciw ? h->C : 1;
-    sh.pin = true;  // accumulator pinning: cfg2 0.244 -> 0.241, cfg5 1.04 -> 0.93 ms
-    sh.U = h->n_codes;
-    sh.scale = (h->flags & PLK_FLAG_SCALING) != 0;
-    // cherries read one product table (plk_jit.hpp: JitUnit) while a fragment's tables stay
-    // within PLK_JIT_PAIR_KB (0: no pairs)
-    const int budget = tune_int("JIT_PAIR_KB", 64, 0, 150) * 1024 / (int)sizeof(double);
-    // One class per workgroup with quad units (plk_jit.hpp JitUnit, JitShape::cls): tables of
-    // one class, so a fragment's cherries fit as 4-tip subtree tables -- for one class per wave,
-    // no rescaling, lnL only (quads are never stored) and at most 4 codes in use (U^4 <= 256).
-    // PLK_TUNE JIT_QUAD_KB bounds the tables (0: off); the plan is rebuilt as usual when it
-    // gets no quad.
-    const bool cls_ok = !h->prog_ciw && !sh.scale && (h->flags & PLK_FLAG_LNL_ONLY) && sh.U <= 4;
-    const int qb = cls_ok ? tune_int("JIT_QUAD_KB", 136, 0, 150) * 1024 / (int)sizeof(double) : 0;
-    if (!h->jit_plan_valid || h->jit_plan_U != sh.U || h->jit_plan_budget != budget || h->jit_plan_qb != qb) {
-      h->jit_plan_cls = false;
-      if (qb > 0) {
-        h->jit_plan = jit_plan(h->prog_host, h->frag_starts_host, sh.C, sh.U, std::max(qb, budget), sh.scale, true, qb);
-        for (const auto& un : h->jit_plan.units)
-          for (const JitUnit& u : un) h->jit_plan_cls |= u.tc >= 0;
-      }
-      if (!h->jit_plan_cls) h->jit_plan = jit_plan(h->prog_host, h->frag_starts_host, sh.C, sh.U, budget, sh.scale);
-      h->jit_plan_valid = true;
-      h->jit_plan_U = sh.U;
-      h->jit_plan_budget = budget;
-      h->jit_plan_qb = qb;
-      h->jit_fn = nullptr;
-      h->ucodes_valid = false;
-    }
-    sh.cls = h->jit_plan_cls;
-    if (!h->ucodes_valid) {
-      std::vector<int4> units;
-      for (const auto& un : h->jit_plan.units)
-        for (const JitUnit& u : un) units.push_back(make_int4(u.ta, u.tb, u.tc, u.td));
-      int rc = ensure_cap(h, (void**)&h->d_ucodes, &h->ucodes_cap, std::max<size_t>(units.size(), 1) * h->n_pad);
-      if (!rc) rc = ensure_cap(h, (void**)&h->d_units, &h->units_cap, std::max<size_t>(units.size(), 1) * sizeof(int4));
-      if (rc) return rc;
-      if (!units.empty()) {
-        HIPCHK(h, hipMemcpyAsync(h->d_units, units.data(), units.size() * sizeof(int4), hipMemcpyHostToDevice,
-                                 h->stream));
-        const dim3 ug((unsigned)((h->n_pad / 16 + 255) / 256), (unsigned)units.size());
-        hipLaunchKernelGGL(unit_codes_kernel, ug, dim3(256), 0, h->stream, h->codes, h->n_pad, h->d_units, sh.U,
-                           h->d_ucodes);
-        HIPCHK(h, hipGetLastError());
-        HIPCHK(h, hipStreamSynchronize(h->stream));  // `units` goes out of scope
-      }
-      h->ucodes_valid = true;
-      h->ucodes_dc_valid = false;
-    }
-    sh.NT = h->jit_plan.NU;
-    sh.TD = h->jit_plan.tab_doubles;
-    sh.QT = h->jit_plan.quad_tmp;
-    sh.soa = tune_int("JIT_SOA", 1, 0, 1) != 0;
-    // direct codes where a fragment has at most 16 units (cfg2, 0.099 vs 0.111 ms traversal);
-    // every class in the wave: up to 32 units in two 16-byte words (cfg5 shard traversal
-    // 345-353 vs 367-368 us; PLK_TUNE JIT_DC_CIW=0 keeps the code rows in LDS)
-    sh.dc = sh.cls ? sh.NT <= 16 && tune_int("JIT_DC", 1, 0, 1) != 0
-                   : h->prog_ciw && sh.NT <= 32 && tune_int("JIT_DC_CIW", 1, 0, 1) != 0;
-    sh.dcw = sh.NT <= 16 ? 1 : 2;
-    if (sh.dc && (!h->ucodes_dc_valid || h->ucodes_dc_w != sh.dcw)) {
-      const int nfr = (int)h->jit_plan.units.size();
-      std::vector<int32_t> us(1, 0);
-      for (const auto& un : h->jit_plan.units) us.push_back(us.back() + (int)un.size());
-      int rc = ensure_cap(h, (void**)&h->d_ucodes_dc, &h->ucodes_dc_cap, (size_t)nfr * h->n_pad * 16 * sh.dcw);
-      if (!rc) rc = ensure_cap(h, (void**)&h->d_units_start, &h->units_start_cap, us.size() * sizeof(int32_t));
-      if (rc) return rc;
-      HIPCHK(h, hipMemcpyAsync(h->d_units_start, us.data(), us.size() * sizeof(int32_t), hipMemcpyHostToDevice,
-                               h->stream));
-      const dim3 dg((unsigned)((h->n_pad + 255) / 256), (unsigned)nfr);
-      hipLaunchKernelGGL(unit_codes_dc_kernel, dg, dim3(256), 0, h->stream, h->d_ucodes, h->n_pad, h->d_units_start,
-                         sh.dcw, reinterpret_cast<uint4*>(h->d_ucodes_dc));
-      HIPCHK(h, hipGetLastError());
-      HIPCHK(h, hipStreamSynchronize(h->stream));  // `us` goes out of scope
-      h->ucodes_dc_valid = true;
-      h->ucodes_dc_w = sh.dcw;
-    }
-    sh.ps1 = tune_int("JIT_PS1", 0, 0, 1) != 0;
-    // pattern groups per workgroup (they share the staged tables): with per-node rescaling
-    // and one class per wave every node has two workgroup barriers, whose cost grows with
-    // the waves that meet there (cfg5: 1.93 ms at G = 2, 1.16 ms at G = 1), so one group;
-    // every class in the wave (no barriers, ~230 VGPRs, two waves per SIMD): eight, the
-    // whole CU's resident waves in one workgroup that stages the tables once (cfg5 at DM 6
-    // with the tier's fragments side by side: G = 6 / 7 / 8 = 0.48 / 0.43 / 0.39 ms);
-    // otherwise the G with the most resident waves (jit_auto_groups; cfg2 with cherry
-    // tables: G = 3, 0.140 ms, G = 2 0.150, G = 4 0.162)
-    // (before G: the code rows take G x PW).  With direct codes (one class per workgroup, no code
-    // rows in LDS) two patterns per lane: twice the independent work per wave at four waves
-    // per SIMD (cfg2 traversal 0.093 vs 0.099 ms)
-    sh.PW = tune_int("JIT_PW", sh.dc && sh.cls ? 2 : 1, 1, 2);
-    sh.G = tune_int("JIT_G", 0, 0, 16);
-    if (sh.G == 0) {
-      if (sh.cls) {
-        // one class per workgroup: the tables take most of the LDS, so one workgroup per CU
-        // and as many groups as fit (at most 16: 1024 threads)
-        sh.G = 16;
-        while (sh.G > 1 && sh.lds_bytes() > 160 * 1024 - 64) --sh.G;
-      } else {
-        sh.G = h->prog_ciw ? 8 : sh.scale ? 1 : jit_auto_groups(sh);
-      }
-    }
-    sh.G = std::max(1, std::min(sh.G, 1024 / (64 * sh.nw())));  // (a JIT_G past 1024 threads)
-    // wave tasks (direct codes, one wave per pattern group): no barrier in the loop, every wave
-    // walks its own 64 * PW-pattern tasks (plk_jit.hpp; PLK_TUNE JIT_WT=0 is the super-block
-    // schedule with its barrier per super-block, kept for A/B runs)
-    // (on for one class per workgroup, where the barrier wait was 22 % of a wave's loop; the
-    // every-class-in-the-wave kernel waits 1.8 % there and keeps the super-block schedule)
-    sh.wt = sh.wt_ok() && tune_int("JIT_WT", sh.cls ? 1 : 0, 0, 1) != 0;
-    // workgroup task pool (wave tasks only; PLK_TUNE JIT_WP=0 is the static stride, kept for A/B
-    // runs): a workgroup's waves draw its tasks (x, x + gridDim.x, ...) from one LDS counter, so
-    // every workgroup owns floor or ceil of n_tasks / gridDim.x tasks and a wave that ran slowly
-    // takes fewer of them (plk_jit.hpp)
-    sh.wp = sh.wt && tune_int("JIT_WP", sh.cls ? 1 : 0, 0, 1) != 0;
-    // two patterns per lane halve the P(t) reads per FMA but double the registers:
-    // measured slower (cfg2 0.255-0.301 vs 0.241 ms), so opt-in; not with speculation
-    // two-stage pipeline, codes / HBM loads 3 ahead (cfg2 0.274 -> 0.259 ms); with every
-    // class in the wave a ring slot is C x larger, so there two events ahead (cfg5 0.385 ms
-    // at L = 2, 0.391 at L = 1; 1.48 vs 1.04 ms at L = 3 vs 1 before the P(t) stream)
-    sh.L = tune_int("JIT_L", h->prog_ciw ? 2 : 3, 1, 8);
-    sh.RD = tune_int("JIT_RD", 1, 1, 8);  // table rows this many fetchers ahead (<= JIT_L)
-    sh.minw = 0;
-    // speculative no-rescale pass (plk_jit.hpp): a win only where rescaling never
-    // fires; on cfg5 it fires in almost every super-block (1.27 vs 1.14 ms), so opt-in
-    // classes in the wave: next class's P(t) loads overlap this class's FMAs
-    sh.ppipe = true;
-    sh.clk = env_is("PLK_DEBUG_CLOCK", '1') ? 1 : env_is("PLK_DEBUG_CLOCK", '2') ? 2 : env_is("PLK_DEBUG_CLOCK", '3') ? 3 : 0;
-    // PLK_JIT_BLOCKS=1: the root fragment forms the block sums (no wave_sums_to_blocks
-    // launch).  Measured slower (cfg2 traversal 0.125 -> 0.160 ms): the wave that stores a
-    // wave sum must wait for the store and the counter's atomic round trip (~3 us) before
-    // its workgroup's next super-block barrier, in every super-block.  Off; the formal
-    // release/acquire form (an L2 write-back per wave) was slower still (round 1).
-    // (That barrier is what wave tasks take out of the loop -- sh.wt above: a round of the
-    // super-block schedule costs what its slowest wave costs.  The class reduction stays a
-    // launch of its own: its handshake would put the same round trip back into every task.)
-    if (sh.lds_bytes() > 160 * 1024 - 64)  // (less the kernel's static LDS word)
-      return fail(h, PLK_ERR_UNSUPPORTED, "tree kernel needs %zu B of LDS", sh.lds_bytes());
-    if (!h->jit_fn || sh.C != h->jit_shape.C || sh.CW != h->jit_shape.CW ||
-        sh.pin != h->jit_shape.pin ||
-        sh.G != h->jit_shape.G || sh.U != h->jit_shape.U ||
-        sh.NT != h->jit_shape.NT || sh.TD != h->jit_shape.TD || sh.scale != h->jit_shape.scale || sh.L != h->jit_shape.L ||
-        sh.minw != h->jit_shape.minw || sh.ppipe != h->jit_shape.ppipe || sh.clk != h->jit_shape.clk ||
-        sh.cls != h->jit_shape.cls || sh.soa != h->jit_shape.soa || sh.ps1 != h->jit_shape.ps1 || sh.RD != h->jit_shape.RD ||
-        sh.dc != h->jit_shape.dc || sh.dcw != h->jit_shape.dcw || sh.wt != h->jit_shape.wt ||
-        sh.wp != h->jit_shape.wp) {
-      int rc = jit_function(h, jit_tree4_source(h->jit_plan, sh), jit_tree4_name(sh), &h->jit_fn);
-      if (rc) return rc;
-      h->jit_shape = sh;
-      h->jit_resident = 0;
-    }
-    ja.partials = a.partials;
-    ja.scale = a.scale;
-    ja.codes = sh.dc ? h->d_ucodes_dc : h->d_ucodes;
-    ja.tipP = h->tipP;
-    ja.weights = a.weights;
-    ja.pi = a.pi;
-    ja.probs = a.probs;
-    ja.site_lnl = a.site_lnl;
-    ja.wave_sums = a.wave_sums;
-    ja.slot_stride = a.slot_stride;
-    ja.n_pad = a.n_pad;
-    ja.n_patterns = a.n_patterns;
-    ja.n_sblocks = (int32_t)((h->n_pad + 64 * sh.G * sh.PW - 1) / (64 * sh.G * sh.PW));  // last may be ragged
-    ja.n_tasks = (int32_t)((h->n_pad + 64 * sh.PW - 1) / (64 * sh.PW));  // (wave tasks; n_pad is whole tiles)
-    ja.guard = a.guard;
-    ja.sb_ctr = h->d_sbctr;
-    ja.dyn = tune_is("JIT_DYN", '0') ? 0 : 1;  // (per launch below)
-    ja.exit_ctr = h->d_sbctr + (size_t)h->prog_nf * h->C;  // (null per launch below when not dynamic)
-    ja.uflow = a.uflow;
-    ja.cls_sum = nullptr;
-    if (sh.cls) {
-      int rc = ensure_cap(h, (void**)&h->d_cls, &h->d_cls_cap, (size_t)h->C * h->n_pad * sizeof(double));
-      if (rc) return rc;
-      ja.cls_sum = h->d_cls;
-    }
+    JitShape sh;
+    int rc = jit4_shape(h, sh);
+    if (!rc) rc = jit4_unit_codes(h, sh);
+    if (!rc) rc = jit4_compile(h, sh);
+    if (!rc) rc = jit4_args(h, a.uflow, ja);
+    if (rc) return rc;
   }
   const bool jitm = kind == FK_TREEM && h->prog_jitm;
   JMArgs ma;
-  JitMShape msh;
   if (jitm) {
-    msh.S = h->S;
-    msh.C = h->C;
-    msh.U = h->n_codes;
-    msh.scale = (h->flags & PLK_FLAG_SCALING) != 0;
-    msh.L = tune_int("JITM_L", 1, 1, 4);
-    msh.minw = 2;
-    msh.pd = 1;
-    // contraction issue order: Y-outer with the A operands read ahead and pinned schedule
-    // groups (plk_jitm.hpp CONTRIB; 3.77 -> 3.26 ms on cfg3); the two-stage operand fetch
-    // loads the code 3 events ahead of its row
-    msh.pipe = 2;
-    msh.lc = 3;
-    msh.G = 4;  // 16-pattern waves per workgroup (64 patterns)
-    if (msh.lds_bytes() > 160 * 1024)
-      return fail(h, PLK_ERR_UNSUPPORTED, "jit_treeM needs %zu B of LDS", msh.lds_bytes());
-    if (!h->jitm_fn || !(msh == h->jitm_shape)) {
-      int rc = jit_function(h, jit_treeM4_source(h->prog_host, h->frag_starts_host, msh), "plk_jit_treeM", &h->jitm_fn);
-      if (rc) return rc;
-      h->jitm_shape = msh;
-    }
-    const CherryLayout lay(h->C, h->n_codes, h->S, h->n_pad);
-    ma.partials = h->partials;
-    ma.scale = h->scale;
-    ma.codes = h->codes;
-    ma.tipP = h->tipP;
-    ma.cherry = h->d_cherry;
-    ma.pmats = h->pmats;
-    ma.weights = h->weights;
-    ma.pi = h->pi;
-    ma.probs = h->probs;
-    ma.site_lnl = h->site_lnl;
-    ma.wave_sums = h->wave_sums;
-    ma.slot_stride = h->slot_stride;
-    ma.n_pad = h->n_pad;
-    ma.n_patterns = h->n_patterns;
-    ma.cherry_stride = (int64_t)lay.stride;
-    ma.cherry_table_bytes = (int64_t)lay.table_bytes;
-    ma.cherry_count_bytes = (int64_t)lay.count_bytes;
-    ma.guard = a.guard;
-    ma.uflow = a.uflow;
+    if (int rc = jitm_compile(h)) return rc;
+    jitm_args(h, a.uflow, ma);
   }
   h->kernel_path = jit ? "jit_tree4" : jitm ? "jit_treeM" : kind == FK_TREEM ? "treeM" : "tree4";
   h->fused_cls_blocks = nullptr;
-  int first = 0;
   if (jit && h->jit_shape.clk) {
-    // stamp buffer for every workgroup of every tier's launch (grids below: at most
-    // jit_resident workgroups per fragment of a tier)
-    size_t need = 0;
-    // (PLK_DEBUG_CLOCK=3: one record per wave; a ragged last workgroup still has all its waves)
-    const size_t per = h->jit_shape.clk == 3 ? (size_t)(h->n_pad / 64 + 16) * h->jit_shape.nw() : (size_t)(h->n_pad / 64);
-    for (const auto& t : h->prog_tiers) need += per * t.size() * (h->jit_shape.cls ? h->C : 1);
-    // The stamps of an evaluation split over several plk_update_partials calls add up: clk_n is
-    // reset where the record is formed (clock_summary), not here.  (Traversals that never reach
-    // a root reduction would grow the buffer without end: past 64 of them the pending stamps are
-    // dropped.)
-    if (h->clk_n > 64 * need) h->clk_n = 0;
-    need += h->clk_n;
-    if (need > h->clk_cap) {
-      unsigned long long *nh = nullptr, *nd = nullptr;
-      if (hipHostMalloc((void**)&nh, need * 4 * sizeof(unsigned long long), hipHostMallocMapped) != hipSuccess ||
-          hipHostGetDevicePointer((void**)&nd, nh, 0) != hipSuccess) {
-        if (nh) hipHostFree(nh);
-        return fail(h, PLK_ERR_OOM, "clock stamp buffer");
-      }
-      if (h->h_clk) {
-        if (h->clk_n) {  // the pending traversals' stamps move along, once their kernels have written them
-          if (int rc = stream_wait(h)) {
-            hipHostFree(nh);
-            return rc;
-          }
-          std::memcpy(nh, h->h_clk, h->clk_n * 4 * sizeof(unsigned long long));
-        }
-        hipHostFree(h->h_clk);
-      }
-      h->h_clk = nh;
-      h->d_clk = nd;
-      h->clk_cap = need;
-    }
+    if (int rc = grow_clock_stamps(h)) return rc;
   }
+  int first = 0;
   for (const auto& t : h->prog_tiers) {
+    const int nfr = (int)t.size();
     a.frag_start = h->d_frag + first;
-    dim3 grid((unsigned)(h->n_pad / 64), (unsigned)t.size());
-    EventPair ev;
-    if (h->timing & PLK_TIME_PARTIALS) {
-      ev = get_events(h, 0);
-      hipEventRecord(ev.a, h->stream);
-    }
+    const dim3 grid((unsigned)(h->n_pad / 64), (unsigned)nfr);
+    TimedSpan span(h, PLK_TIME_PARTIALS, 0);
     if (jit) {
-      const double* pm = h->pmats;
-      int base = first;
-      const int gz = sh.cls ? h->C : 1;  // one class per workgroup: grid.z = class
-      unsigned long long* clkp = h->d_clk ? h->d_clk + 4 * h->clk_n : nullptr;
-      void* args[] = {&ja, &pm, &base, &clkp};  // (the 4th only exists in a PLK_DEBUG_CLOCK build)
-      // persistent grid: as many workgroups as are resident at once (occupancy query), so
-      // every workgroup stages its tables once and there is no second dispatch round
-      int wgs = 0;
-      {
-        if (h->jit_resident <= 0) {
-          int per_cu = 0, n_cu = 0;
-          HIPCHK(h, hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, h->jit_fn, 64 * sh.nw() * sh.G,
-                                                                       sh.lds_bytes()));
-          HIPCHK(h, hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, h->device));
-          h->jit_resident = std::max(1, per_cu) * std::max(1, n_cu);
-        }
-        // every fragment of the tier at once: the resident workgroups split over the
-        // fragments (each stages its fragment's tables once and walks many super-blocks)
-        // instead of the tier's fragments running one after another with every workgroup
-        // staging tables for a few super-blocks (cfg5 0.49 -> 0.42 ms)
-        wgs = std::max(1, h->jit_resident / ((int)grid.y * gz));
-        // PLK_TUNE JIT_WGS=<n>: at most n persistent workgroups per (fragment, class), so that a
-        // few thousand patterns walk many tasks per workgroup (the dynamic order in small tests)
-        if (const int cap = tune_int("JIT_WGS", 0, 0, 1 << 20)) wgs = std::min(wgs, cap);
-      }
-      const unsigned gx = (unsigned)std::min<int64_t>(ja.n_sblocks, wgs);
-      // dynamic super-blocks where a workgroup walks several (a tier of 1-2 per workgroup
-      // gains nothing from them and pays the counter's round trips); wave tasks: where a wave
-      // walks at least three
-      const int64_t units = sh.wt ? ja.n_tasks : ja.n_sblocks, walkers = sh.wt ? (int64_t)gx * sh.G : (int64_t)gx;
-      // (wave tasks take tickets only when asked to, JIT_DYN=1: one ticket per 128-pattern task
-      // is 16 x the atomics on the same counter words, and at cfg2's 1 M patterns -- 7 813
-      // tasks per class over 1 024 waves -- the traversal ran 388 us against 83 with the
-      // super-block schedule, profiles/r07/ab_runs.md; the static stride needs none)
-      // (a task-pool program takes its tickets from LDS: no global counter, no exit ticket)
-      const bool dyn_on = sh.wp ? false : sh.wt ? tune_is("JIT_DYN", '1') : !tune_is("JIT_DYN", '0');
-      ja.dyn = (dyn_on && units >= 3 * walkers) ? 1 : 0;
-      // the launch's counters start at 0; its last workgroup leaves them at 0 (exit ticket)
-      ja.exit_ctr = ja.dyn ? h->d_sbctr + (size_t)h->prog_nf * h->C : nullptr;
-      h->jit_last_gx = (int)gx;
-      if ((int)h->jit_frag_gx.size() < h->prog_nf) h->jit_frag_gx.resize((size_t)h->prog_nf, 0);
-      for (int k = 0; k < (int)t.size(); ++k) h->jit_frag_gx[(size_t)(first + k)] = (int)gx;
-      HIPCHK(h, hipModuleLaunchKernel(h->jit_fn, gx, grid.y, (unsigned)gz, 64 * sh.nw() * sh.G, 1, 1,
-                                      (unsigned)sh.lds_bytes(),
-                                      h->stream, args, nullptr));
-      if (sh.clk) h->clk_n += (size_t)gx * grid.y * gz * (sh.clk == 3 ? (size_t)sh.nw() * sh.G : 1);
-      if (sh.cls && h->prog_root >= 0 && first + (int)t.size() == h->prog_nf) {
-        // the classes' root terms meet here: log, site lnL, wave and block sums (the work of
-        // reduce_root and wave_sums_to_blocks), inside the traversal's timing
-        h->fused_cls_blocks = block_target(h);
-        if (int rc = launch_cls_blocks(h, ja.guard, ja.uflow, false)) return rc;
-      }
+      if (int rc = launch_jit_tree4(h, ja, first, nfr)) return rc;
     } else if (jitm) {
-      int base = first;
-      void* args[] = {&ma, &base};
-      HIPCHK(h, hipModuleLaunchKernel(h->jitm_fn, (unsigned)(h->n_pad / (16 * msh.G)), grid.y, 1,
-                                      64 * msh.G, 1, 1, (unsigned)msh.lds_bytes(), h->stream, args, nullptr));
+      if (int rc = launch_jit_treeM(h, ma, first, nfr)) return rc;
     } else if (kind == FK_TREEM) {
       launch_treeM(h, a, grid, lds_m);
-      if (treeM_groups(h) != kTreeMGroups && h->prog_root >= 0 && first + (int)t.size() == h->prog_nf) {
+      if (treeM_groups(h) != kTreeMGroups && h->prog_root >= 0 && first + nfr == h->prog_nf) {
         // 32-pattern workgroups: the root's 64-pattern wave sums from site_lnl
         site_wave_sums_kernel<<<(unsigned)(h->n_pad / 256), 256, 0, h->stream>>>(a.site_lnl, a.weights,
                                                                                  a.wave_sums, a.n_patterns, a.n_pad);
@@ -2494,16 +2557,11 @@ int update_tree4(plk_handle h, const plk_op* ops, int n_ops) {
       launch_tree4(h, a, grid, lds);
     }
     HIPCHK(h, hipGetLastError());
-    if (h->timing & PLK_TIME_PARTIALS) {
-      hipEventRecord(ev.b, h->stream);
-      h->events.push_back(ev);
-    }
-    if (h->timing & PLK_TIME_PARTIALS) h->n_launches++;  // launches timed by the events
-    first += (int)t.size();
+    if (span.stop()) h->n_launches++;  // launches timed by the events
+    first += nfr;
   }
   h->fused_lnl_valid = h->prog_root >= 0;
   h->fused_lnl_root = h->prog_root;
-  // the jit kernel's root fragment formed the block sums (JitShape::blocks)
   return PLK_OK;
 }
 
@@ -2583,11 +2641,7 @@ int update_levelwise(plk_handle h, const plk_op* ops, int n_ops) {
     const int cnt = level_start[l + 1] - level_start[l];
     if (cnt == 0) continue;
     const KOp* d = h->d_ops + level_start[l];
-    EventPair ev;
-    if (h->timing & PLK_TIME_PARTIALS) {
-      ev = get_events(h, 0);
-      hipEventRecord(ev.a, h->stream);
-    }
+    TimedSpan span(h, PLK_TIME_PARTIALS, 0);
     if (s4) {
       if (h->flags & PLK_FLAG_SCALING)
         launch_s4<true>(h, d, cnt, a);
@@ -2598,11 +2652,7 @@ int update_levelwise(plk_handle h, const plk_op* ops, int n_ops) {
       if (rc) return rc;
     }
     HIPCHK(h, hipGetLastError());
-    if (h->timing & PLK_TIME_PARTIALS) {
-      hipEventRecord(ev.b, h->stream);
-      h->events.push_back(ev);
-    }
-    if (h->timing & PLK_TIME_PARTIALS) h->n_launches++;  // launches timed by the events
+    if (span.stop()) h->n_launches++;  // launches timed by the events
   }
   for (int i = 0; i < n_ops; ++i) h->materialized[ops[i].parent - h->n_tips] = 1;
   h->fused_lnl_valid = false;
@@ -2886,11 +2936,7 @@ int update_compressed(plk_handle h, const plk_op* ops, int n_ops) {
     const int cnt = h->cmp_level_start[l + 1] - h->cmp_level_start[l];
     if (cnt == 0) continue;
     const KOpL* d = h->d_opsl + h->cmp_level_start[l];
-    EventPair ev;
-    if (h->timing & PLK_TIME_PARTIALS) {
-      ev = get_events(h, 0);
-      hipEventRecord(ev.a, h->stream);
-    }
+    TimedSpan span(h, PLK_TIME_PARTIALS, 0);
     const int maxD = h->cmp_level_maxD[l];
     if (h->S == 4 && s4_supported(h->C)) {
       switch (h->C) {
@@ -2904,11 +2950,7 @@ int update_compressed(plk_handle h, const plk_op* ops, int n_ops) {
       if (rc2) return rc2;
     }
     HIPCHK(h, hipGetLastError());
-    if (h->timing & PLK_TIME_PARTIALS) {
-      hipEventRecord(ev.b, h->stream);
-      h->events.push_back(ev);
-    }
-    if (h->timing & PLK_TIME_PARTIALS) h->n_launches++;  // launches timed by the events
+    if (span.stop()) h->n_launches++;  // launches timed by the events
   }
   for (int i = 0; i < n_ops; ++i) h->materialized[ops[i].parent - h->n_tips] = 1;
   h->fused_lnl_valid = false;
@@ -3498,11 +3540,7 @@ int dr_fused_preorder(plk_handle h, const std::vector<std::vector<int> >& depth,
   a.C = C;
   a.n_blk = n_blk;
   a.uout = h->partials;
-  EventPair ev;
-  if (h->timing & PLK_TIME_PARTIALS) {
-    ev = get_events(h, 0);
-    hipEventRecord(ev.a, h->stream);
-  }
+  TimedSpan span(h, PLK_TIME_PARTIALS, 0);
   for (const Level& l : levels) {
     const dim3 grid((unsigned)n_blk, (unsigned)l.count);
     const DrPreOp* o = h->d_drpre + l.first;
@@ -3533,10 +3571,7 @@ int dr_fused_preorder(plk_handle h, const std::vector<std::vector<int> >& depth,
     }
     HIPCHK(h, hipGetLastError());
   }
-  if (h->timing & PLK_TIME_PARTIALS) {
-    hipEventRecord(ev.b, h->stream);
-    h->events.push_back(ev);
-  }
+  span.stop();
   dr_sum_kernel<<<(unsigned)br.size(), 256, 0, h->stream>>>(h->d_drb, a.blk1, a.blk2, n_blk, h->dr_out, h->dr_out + nn);
   HIPCHK(h, hipGetLastError());
   std::vector<double> out(2 * (size_t)nn);
@@ -3725,11 +3760,7 @@ int dr_derivatives(plk_handle h, double* d1, double* d2) {
   a.G = 3 * (size_t)C * S * S * sizeof(double) <= 96 * 1024 ? C : 1;
   dim3 grid((unsigned)n_blk, (unsigned)br.size());
   const size_t lds = 3 * (size_t)a.G * S * S * sizeof(double);
-  EventPair ev;
-  if (h->timing & PLK_TIME_PARTIALS) {
-    ev = get_events(h, 0);
-    hipEventRecord(ev.a, h->stream);
-  }
+  TimedSpan span(h, PLK_TIME_PARTIALS, 0);
   if (dr_mfma) {
     DrArgs am = a;
     am.G = 3 * (size_t)C * S * S * sizeof(double) <= 64 * 1024 ? C : 1;
@@ -3749,10 +3780,7 @@ int dr_derivatives(plk_handle h, double* d1, double* d2) {
     }
   }
   HIPCHK(h, hipGetLastError());
-  if (h->timing & PLK_TIME_PARTIALS) {
-    hipEventRecord(ev.b, h->stream);
-    h->events.push_back(ev);
-  }
+  span.stop();
   dr_sum_kernel<<<(unsigned)br.size(), 256, 0, h->stream>>>(h->d_drb, a.blk1, a.blk2, n_blk, h->dr_out, h->dr_out + nn);
   HIPCHK(h, hipGetLastError());
   std::vector<double> out(2 * (size_t)nn);
@@ -3866,11 +3894,7 @@ int node_posteriors_local(plk_handle h, int n_nodes, const int32_t* nodes, doubl
     a.C = C;
     a.n_blk = (int)(h->n_pad / 64);
     a.G = (size_t)C * S * S * sizeof(double) <= 64 * 1024 ? C : 1;
-    EventPair ev;
-    if (h->timing & PLK_TIME_PARTIALS) {
-      ev = get_events(h, 0);
-      hipEventRecord(ev.a, h->stream);
-    }
+    TimedSpan span(h, PLK_TIME_PARTIALS, 0);
     if (mfma && tune_int("POST_VALU", 0, 0, 1)) {
       const dim3 grid((unsigned)(h->n_pad / kPostThreads), (unsigned)cn);
       const size_t lds = (size_t)S * S * sizeof(double);
@@ -3904,11 +3928,7 @@ int node_posteriors_local(plk_handle h, int n_nodes, const int32_t* nodes, doubl
 #undef PLK_POST_S
     }
     HIPCHK(h, hipGetLastError());
-    if (h->timing & PLK_TIME_PARTIALS) {
-      hipEventRecord(ev.b, h->stream);
-      h->events.push_back(ev);
-      h->n_launches++;
-    }
+    if (span.stop()) h->n_launches++;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     // rows [node][k][n_pad] -> the caller's [node][pattern][k]
     auto rows_out = [&](const double* dev, int K, double* out) -> int {
@@ -4081,17 +4101,9 @@ int map_fill_tip_uppers(plk_handle h, const std::vector<int>& tips, const std::v
   HIPCHK(h, hipMemcpyAsync(h->d_ops, flat.data(), flat.size() * sizeof(KOp), hipMemcpyHostToDevice, h->stream));
   h->last_ops.clear();  // d_ops now holds these ops
   for (auto& l : launches) {
-    EventPair ev;
-    if (h->timing & PLK_TIME_PARTIALS) {
-      ev = get_events(h, 0);
-      hipEventRecord(ev.a, h->stream);
-    }
+    TimedSpan span(h, PLK_TIME_PARTIALS, 0);
     if ((rc = launch_partials_ops(h, h->d_ops + l.first, l.second))) return rc;
-    if (h->timing & PLK_TIME_PARTIALS) {
-      hipEventRecord(ev.b, h->stream);
-      h->events.push_back(ev);
-      h->n_launches++;
-    }
+    if (span.stop()) h->n_launches++;
   }
   HIPCHK(h, hipStreamSynchronize(h->stream));  // flat is read by the copy
   for (int v : todo) h->tipu_epoch[v] = h->state_epoch;
@@ -4191,11 +4203,7 @@ int branch_counts_local(plk_handle h, int n_branches, const int32_t* branches, d
     a.n_blk = n_blk;
     const int NM = (T + 1) * C;
     a.G = (int)std::min<size_t>((size_t)NM, std::max<size_t>(1, (size_t)64 * 1024 / ((size_t)S * S * sizeof(double))));
-    EventPair ev;
-    if (h->timing & PLK_TIME_PARTIALS) {
-      ev = get_events(h, 0);
-      hipEventRecord(ev.a, h->stream);
-    }
+    TimedSpan span(h, PLK_TIME_PARTIALS, 0);
     if (mfma) {
       // a few workgroups per branch, each looping over 64-pattern blocks (8192 in total)
       const unsigned gx = (unsigned)std::min<int64_t>(n_blk, std::max<int64_t>(1, (8192 + cn - 1) / cn));
@@ -4222,11 +4230,7 @@ int branch_counts_local(plk_handle h, int n_branches, const int32_t* branches, d
 #undef PLK_MAP_S
     }
     HIPCHK(h, hipGetLastError());
-    if (h->timing & PLK_TIME_PARTIALS) {
-      hipEventRecord(ev.b, h->stream);
-      h->events.push_back(ev);
-      h->n_launches++;
-    }
+    if (span.stop()) h->n_launches++;
     double* d_out = nullptr;
     if (blocks) {
       d_out = h->map_blk + (size_t)cn * T * n_blk;
@@ -4691,18 +4695,11 @@ static int launch_root(plk_handle h, int root) {
   a.C = h->C;
   a.guard = (h->flags & PLK_FLAG_NONNEG_GUARD) ? 1 : 0;
   a.uflow = uflow_arm(h);
-  EventPair ev;
-  if (h->timing & PLK_TIME_ROOT) {
-    ev = get_events(h, 2);
-    hipEventRecord(ev.a, h->stream);
-  }
+  TimedSpan span(h, PLK_TIME_ROOT, 2);
   root_kernel<<<(unsigned)(h->n_pad / 64), 64, 0, h->stream>>>(a);
   HIPCHK(h, hipGetLastError());
   if (int rc = launch_block_sums(h)) return rc;
-  if (h->timing & PLK_TIME_ROOT) {
-    hipEventRecord(ev.b, h->stream);
-    h->events.push_back(ev);
-  }
+  span.stop();
   return PLK_OK;
 }
 
@@ -5050,11 +5047,7 @@ int plk_update_count_matrices(plk_handle h, int n, const int32_t* branch, const 
   a.C = C;
   a.T = h->count_T;
   a.n_req = n;
-  EventPair ev;
-  if (h->timing & PLK_TIME_PMAT) {
-    ev = get_events(h, 1);
-    hipEventRecord(ev.a, h->stream);
-  }
+  TimedSpan span(h, PLK_TIME_PMAT, 1);
   if (S <= 4) {
     const unsigned g4 = (unsigned)((n * C * S + 63) / 64);
     switch (S) {
@@ -5066,10 +5059,7 @@ int plk_update_count_matrices(plk_handle h, int n, const int32_t* branch, const 
     count_matrix_kernel<<<dim3(n, C), 256, 2 * (size_t)S * S * sizeof(double), h->stream>>>(a);
   }
   HIPCHK(h, hipGetLastError());
-  if (h->timing & PLK_TIME_PMAT) {
-    hipEventRecord(ev.b, h->stream);
-    h->events.push_back(ev);
-  }
+  span.stop();
   HIPCHK(h, hipStreamSynchronize(h->stream));  // req is read by the copy
   for (int i = 0; i < n; ++i) h->wmat_valid[branch[i]] = 1;
   return PLK_OK;

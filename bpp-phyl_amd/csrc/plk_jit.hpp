@@ -30,6 +30,7 @@
 
 #include <algorithm>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include "plk_tree4.hpp"
@@ -420,6 +421,7 @@ static const char* kJitArgsTail = "[C][n_pad]\n};";
 static const char* kJitArgsTailWt = "[C][n_pad]\n  i32 n_tasks;  // wave tasks (64 * PW_ patterns each)\n};";
 
 struct JitShape {
+  // a new field goes into tied() too: operator== decides whether a compiled kernel still fits
   int C = 1;        // rate classes
   int CW = 1;       // classes per wave (1, or C: a wave holds every class of its patterns)
   int PW = 1;       // patterns per lane (1 or 2: p and p + 64 share every P(t) read)
@@ -456,6 +458,10 @@ struct JitShape {
   // (jit_pool_task) and its waves draw them from one LDS counter, whichever wave is free next --
   // no global atomic, no barrier, no wave waiting for another
   bool wp = false;
+  auto tied() const {
+    return std::tie(C, CW, PW, pin, G, U, NT, TD, scale, L, RD, minw, ppipe, clk, cls, QT, soa, ps1, dc, dcw, wt, wp);
+  }
+  bool operator==(const JitShape& o) const { return tied() == o.tied(); }
   int nw() const { return cls ? 1 : C / CW; }  // waves per pattern group
   bool wt_ok() const { return dc && nw() == 1; }
   size_t lds_bytes() const {

@@ -44,6 +44,7 @@
 
 #include <algorithm>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include "plk_tree4.hpp"
@@ -106,6 +107,7 @@ struct JMArgs {
 };
 
 struct JitMShape {
+  // a new field goes into tied() too (operator==)
   int S = 20;
   int C = 1;
   int U = 1;         // codes in use (rows of a tip table; cherry tables have U * U)
@@ -123,10 +125,8 @@ struct JitMShape {
   // then drains every outstanding load, the operand prefetches included, before it)
   int pbs() const { const int nth = 64 * G; return (pb() + nth - 1) / nth * nth; }
   size_t lds_bytes() const { return (size_t)(2 * pbs() + 16 * G) * sizeof(double); }
-  bool operator==(const JitMShape& o) const {
-    return S == o.S && C == o.C && U == o.U && scale == o.scale && L == o.L && minw == o.minw && pd == o.pd &&
-           G == o.G && pipe == o.pipe && lc == o.lc;
-  }
+  auto tied() const { return std::tie(S, C, U, scale, L, minw, pd, G, lc, pipe); }
+  bool operator==(const JitMShape& o) const { return tied() == o.tied(); }
 };
 
 // Emit the kernel for build_tree4_program's words `prog` and fragment start offsets

@@ -120,6 +120,28 @@ def test_one_pattern_per_lane(monkeypatch):
     _problem_case(monkeypatch, Problem(4, 4, "balanced64", 700), {"JIT_PW": "1"})
 
 
+def test_retune_on_a_live_handle(monkeypatch):
+    """PLK_TUNE is read again at every call, so a handle that has evaluated must follow a tune that
+    changes afterwards: one engine evaluates under the default tunes, JIT_PW=1, JIT_PW=2, JIT_WP=0
+    and JIT_G=16 in turn, each time bitwise equal to a fresh engine under the same tunes.  700
+    patterns pad to six 128-pattern tasks at PW = 2 and twelve 64-pattern tasks at PW = 1: a kernel
+    compiled for one and launched with the other's task count cannot give the per-pattern values."""
+    p = Problem(4, 4, "balanced64", 700)
+    live = p.engine(LNL | GUARD)
+    for tune in ({}, {"JIT_PW": "1"}, {"JIT_PW": "2"}, {"JIT_WP": "0"}, {"JIT_G": "16"}):
+        with monkeypatch.context() as mp:
+            for k, v in tune.items():
+                set_tune(mp, k, v)
+            res = run_engine(live, p.et)
+            assert live.kernel_path() == "jit_tree4", tune
+            fresh = p.engine(LNL | GUARD)
+            ref = run_engine(fresh, p.et)
+            fresh.close()
+        assert len(res[1]) == p.n
+        _same(res, ref, str(tune))
+    live.close()
+
+
 @pytest.mark.parametrize("guard", [True, False], ids=["guard", "noguard"])
 def test_root_rules(guard, monkeypatch):
     """Both root rules: terms <= 0 dropped per state and class | every term added and the site
