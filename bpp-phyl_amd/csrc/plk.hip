@@ -15,6 +15,7 @@
 #include "plk_dr.hpp"
 #include "plk_post.hpp"
 #include "plk_map.hpp"
+#include "plk_nni.hpp"
 #include "plk_exchange.hpp"
 
 #include <hip/hip_runtime.h>
@@ -411,6 +412,14 @@ struct plk_handle_s {
   size_t map_blk_cap = 0;
   char* d_mapreq = nullptr;             // a count-matrix request: t, branch, model
   size_t d_mapreq_cap = 0;
+  // NNI scoring (plk_nni.hpp): the coefficient rows of a chunk of moves live in post_buf, the
+  // workgroup and block sums of a pass in map_blk
+  char* d_nni = nullptr;                // a chunk's move records; a pass's active list, models, lengths, exponents
+  size_t d_nni_cap = 0;
+  double* nni_vit = nullptr;            // Vinv^T per model (nni_coef_mfma_kernel)
+  char* h_nni = nullptr;                // pinned: a pass's request and its block sums
+  size_t h_nni_cap = 0;
+  int64_t nni_passes = 0;               // evaluation passes of the last plk_nni_scores (plk_nni_passes)
   // multi-device handle (plk_create_multi): one shard handle per device over contiguous,
   // block-aligned pattern ranges; the parent owns no device memory
   std::vector<plk_handle> shards;
@@ -1212,13 +1221,14 @@ int plk_destroy(plk_handle h) {
                   h->d2_sums, h->d_dprog, h->pmatsT, h->d_ucodes, h->d_units, h->d_cherry3,
                   h->d_cherry_tips, h->d_cherry, h->d_drb, h->d_drm, h->dr_blk, h->dr_out, h->d_drpre, h->d_sbctr,
                   h->d_cherry_rows, h->d_kidsl, h->d_cls, h->d_ucodes_dc, h->d_units_start, h->d_post, h->post_buf,
-                  h->count_G, h->wmats, h->d_mapb, h->map_blk, h->d_mapreq};
+                  h->count_G, h->wmats, h->d_mapb, h->map_blk, h->d_mapreq, h->d_nni, h->nni_vit};
   for (void* p : bufs)
     if (p) hipFree(p);
   if (h->h_req) (void)hipHostFree(h->h_req);
   if (h->h_blocks) hipHostFree(h->h_blocks);
   if (h->h_uflow) hipHostFree(h->h_uflow);
   if (h->h_clk) hipHostFree(h->h_clk);
+  if (h->h_nni) (void)hipHostFree(h->h_nni);
   if (h->req_done) hipEventDestroy(h->req_done);
   for (auto& e : h->events) {
     hipEventDestroy(e.a);
@@ -4261,6 +4271,236 @@ int branch_counts_local(plk_handle h, int n_branches, const int32_t* branches, d
   }
   return PLK_OK;
 }
+
+// ---------------------------------------------------------------------------
+// NNI scoring (plk_nni.hpp): two local stages, "build the coefficient rows of a chunk of
+// moves" and "evaluate a chunk at t[]", driven by the Newton loop of plk_nni_scores -- on a
+// multi-device handle by the parent, over the shards' block sums in global block order.
+// ---------------------------------------------------------------------------
+constexpr size_t kNniStageCap = (size_t)2 << 30;  // coefficient rows of one chunk of moves (a move of cfg2: 144 MB)
+
+// The checks of plk_nni_scores that need the tree, and the move records.  g_pi is set for a g
+// that is a son of the root; the build clears it where the preorder pass folded pi into U_g.
+int nni_plan(plk_handle h, int n_moves, const int32_t* son, const int32_t* uncle, const int32_t* model,
+             std::vector<NniMove>& recs) {
+  const int S = h->S, nt = h->n_tips, nn = h->n_nodes;
+  if (h->comm) return fail(h, PLK_ERR_UNSUPPORTED, "NNI scoring under a communicator");
+  if (h->flags & PLK_FLAG_SUBTREE_PATTERNS)
+    return fail(h, PLK_ERR_UNSUPPORTED, "NNI scoring reads full-length partials (no pattern compression)");
+  if (!(h->flags & PLK_FLAG_DOUBLE_RECURSIVE))
+    return fail(h, PLK_ERR_STATE, "handle was not created with PLK_FLAG_DOUBLE_RECURSIVE");
+  if (h->trav_ops.empty()) return fail(h, PLK_ERR_STATE, "no traversal yet (plk_update_partials)");
+  if (!(S == 2 || S == 3 || S == 4 || S == 20 || S == 64))
+    return fail(h, PLK_ERR_UNSUPPORTED, "state count %d has no kernel instance", S);
+  std::vector<int> parent(nn, -1);
+  for (int n = 0; n < nn; ++n)
+    for (int c : h->topo_kids[n]) parent[c] = n;
+  int root = h->trav_ops.back().parent;
+  while (parent[root] >= 0) root = parent[root];
+  std::vector<char> in_tree(nn, 0);
+  {
+    std::vector<int> st(1, root);
+    while (!st.empty()) {
+      const int n = st.back();
+      st.pop_back();
+      in_tree[n] = 1;
+      for (int c : h->topo_kids[n]) st.push_back(c);
+    }
+  }
+  auto kid = [&](int v) {
+    NniKid k;
+    k.kind = v < 0 ? 2 : v < nt ? 1 : 0;
+    k.child = v < 0 ? 0 : v < nt ? v : v - nt;
+    k.node = v < 0 ? 0 : v;
+    return k;
+  };
+  recs.resize((size_t)n_moves);
+  for (int i = 0; i < n_moves; ++i) {
+    const int s = son[i], u = uncle[i], m = model ? model[i] : 0;
+    if (s < 0 || s >= nn || u < 0 || u >= nn) return fail(h, PLK_ERR_ARG, "move %d: node out of range (%d, %d)", i, s, u);
+    if (!in_tree[s] || !in_tree[u]) return fail(h, PLK_ERR_ARG, "move %d: (%d, %d) is not in the current tree", i, s, u);
+    if (s == root || parent[s] == root) return fail(h, PLK_ERR_ARG, "move %d: son %d is the root or a son of the root", i, s);
+    const int p = parent[s], g = parent[p];
+    if (u == p || parent[u] != g) return fail(h, PLK_ERR_ARG, "move %d: %d is no uncle of %d", i, u, s);
+    if (m < 0 || m >= h->n_models) return fail(h, PLK_ERR_ARG, "move %d: model %d out of range", i, m);
+    const std::vector<int>&kp = h->topo_kids[p], &kg = h->topo_kids[g];
+    if (kp.size() > 3 || kg.size() > 3 || kp.size() < 2)
+      return fail(h, PLK_ERR_UNSUPPORTED, "move %d: node %d (%zu sons) or %d (%zu sons) has more than three sons, or the first only one",
+                  i, p, kp.size(), g, kg.size());
+    if (!h->eigen_set[m]) return fail(h, PLK_ERR_STATE, "eigen system %d not set", m);
+    NniMove& r = recs[(size_t)i];
+    std::memset(&r, 0, sizeof(r));
+    int og = -1, op[2] = {-1, -1}, n = 0;
+    for (int o : kg)
+      if (o != p && o != u) og = o;
+    for (int o : kp)
+      if (o != s) op[n++] = o;
+    r.k[0] = kid(s);
+    r.k[1] = kid(u);
+    r.k[2] = kid(og);
+    r.k[3] = kid(op[0]);
+    r.k[4] = kid(op[1]);
+    r.g_node = g;
+    r.g_uslot = h->dr_slot0 + g;
+    r.g_root = g == root;
+    r.g_pi = g != root && parent[g] == root;
+    r.p_node = p;
+    r.model = m;
+  }
+  return PLK_OK;
+}
+
+// carve-up of d_nni for chunks of at most `chunk` moves
+struct NniStage {
+  // req: a pass's request, packed for one copy: 2 n_act lengths, n_act moves, n_act models
+  size_t moves, req, ex, bytes;
+  static size_t req_bytes(int n) { return (size_t)n * (2 * sizeof(double) + 2 * sizeof(int32_t)); }
+  NniStage(int chunk, int CS) {
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    moves = 0;
+    req = up((size_t)chunk * sizeof(NniMove));
+    ex = req + up(req_bytes(chunk));
+    bytes = ex + up((size_t)chunk * (4 * CS + 2) * sizeof(double));
+  }
+};
+
+// Stage 1: the coefficient rows [move][C S + kNniExtra][n_pad] of `cn` moves into post_buf
+// (first: the call's first chunk, which also prepares what every chunk shares).
+int nni_build_local(plk_handle h, const NniMove* recs, int cn, int chunk, bool first) {
+  const int S = h->S, C = h->C, CS = C * S;
+  hipSetDevice(h->device);
+  int rc;
+  // the preorder pass, unless the last one still holds
+  if (h->dr_u_epoch != h->state_epoch && (rc = dr_derivatives(h, nullptr, nullptr))) return rc;
+  const bool mfma = S == 20 || S == 64;
+  if (mfma) {
+    if ((rc = ensure_pmatsT(h))) return rc;
+    if (!h->nni_vit && (rc = dalloc(h, (void**)&h->nni_vit, (size_t)h->n_models * S * S * sizeof(double)))) return rc;
+    if (first) {  // once per call: the eigen systems do not change under it
+      nni_transpose_kernel<<<(unsigned)h->n_models, 256, 0, h->stream>>>(h->Vinv, h->nni_vit, S);
+      HIPCHK(h, hipGetLastError());
+    }
+  }
+  const NniStage st(chunk, CS);
+  if ((rc = ensure_cap(h, (void**)&h->post_buf, &h->post_buf_cap, (size_t)chunk * (CS + kNniExtra) * h->n_pad * sizeof(double))))
+    return rc;
+  if ((rc = ensure_cap(h, (void**)&h->d_nni, &h->d_nni_cap, st.bytes))) return rc;
+  // pinned staging of a pass: the request going up, the block sums coming back
+  const size_t pin = NniStage::req_bytes(chunk) + (size_t)chunk * kNniSums * h->n_blocks * sizeof(double);
+  if (h->h_nni_cap < pin) {
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (h->h_nni) (void)hipHostFree(h->h_nni);
+    h->h_nni = nullptr;
+    h->h_nni_cap = 0;
+    HIPCHK(h, hipHostMalloc((void**)&h->h_nni, pin, hipHostMallocDefault));
+    h->h_nni_cap = pin;
+  }
+  std::vector<NniMove> mv(recs, recs + cn);
+  for (NniMove& r : mv) r.g_pi = r.g_pi && !h->dr_u_pi;
+  HIPCHK(h, hipMemcpyAsync(h->d_nni + st.moves, mv.data(), mv.size() * sizeof(NniMove), hipMemcpyHostToDevice, h->stream));
+  const NniMove* d_mv = reinterpret_cast<const NniMove*>(h->d_nni + st.moves);
+  NniArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.partials = h->partials;
+  a.codes = h->codes;
+  a.code_table = h->code_table;
+  a.pmats = h->pmats;
+  a.pmatsT = h->pmatsT;
+  a.V = h->V;
+  a.Vinv = mfma ? h->nni_vit : h->Vinv;
+  a.pi = h->pi;
+  a.probs = h->probs;
+  a.coef = (double*)h->post_buf;
+  a.slot_stride = h->slot_stride;
+  a.n_pad = h->n_pad;
+  a.C = C;
+  a.n_blk = (int)(h->n_pad / 64);
+  TimedSpan span(h, PLK_TIME_PARTIALS, 0);
+  if (mfma) {
+    // a few workgroups per move, each looping over 64-pattern blocks (8192 in total)
+    const unsigned gx = (unsigned)std::min<int64_t>(a.n_blk, std::max<int64_t>(1, (8192 + cn - 1) / cn));
+    const size_t lds = (size_t)S * S * sizeof(double);
+    if (S == 20)
+      nni_coef_mfma_kernel<20><<<dim3(gx, (unsigned)cn), kNniThreads, lds, h->stream>>>(d_mv, a);
+    else
+      nni_coef_mfma_kernel<64><<<dim3(gx, (unsigned)cn), kNniThreads, lds, h->stream>>>(d_mv, a);
+  } else {
+    const dim3 grid((unsigned)(h->n_pad / kNniThreads), (unsigned)cn);
+#define PLK_NNI_S(S_)                                                                          \
+  switch (C) {                                                                                 \
+    case 1: nni_coef_s4_kernel<S_, 1><<<grid, kNniThreads, 0, h->stream>>>(d_mv, a); break;    \
+    case 2: nni_coef_s4_kernel<S_, 2><<<grid, kNniThreads, 0, h->stream>>>(d_mv, a); break;    \
+    case 3: nni_coef_s4_kernel<S_, 3><<<grid, kNniThreads, 0, h->stream>>>(d_mv, a); break;    \
+    case 4: nni_coef_s4_kernel<S_, 4><<<grid, kNniThreads, 0, h->stream>>>(d_mv, a); break;    \
+    default: nni_coef_s4_kernel<S_, 0><<<grid, kNniThreads, 0, h->stream>>>(d_mv, a); break;   \
+  }
+    switch (S) {
+      case 2: PLK_NNI_S(2) break;
+      case 3: PLK_NNI_S(3) break;
+      case 4: PLK_NNI_S(4) break;
+    }
+#undef PLK_NNI_S
+  }
+  HIPCHK(h, hipGetLastError());
+  if (span.stop()) h->n_launches++;
+  HIPCHK(h, hipStreamSynchronize(h->stream));  // mv is read by the copy
+  return PLK_OK;
+}
+
+// Stage 2: the moves idx[] of the built chunk at the lengths t[0 .. n_act), their accepted points
+// at t[n_act .. 2 n_act): blocks [n_act][kNniSums][nB_total] gets this handle's sums of w log rho,
+// w rho'/rho, w (rho''/rho - (rho'/rho)^2) and w log(rho(t) / rho(t_acc)) per kRootBlock
+// patterns, from block B0 on.
+int nni_eval_local(plk_handle h, int chunk, int n_act, const int32_t* idx, const int32_t* model, const double* t,
+                   double* blocks, int64_t nB_total, int64_t B0) {
+  const int S = h->S, C = h->C, CS = C * S;
+  hipSetDevice(h->device);
+  int rc;
+  const NniStage st(chunk, CS);
+  const int n_blk = (int)(h->n_pad / kNniThreads), per = kRootBlock / kNniThreads, nB = h->n_blocks;
+  if ((rc = ensure_cap(h, (void**)&h->map_blk, &h->map_blk_cap, (size_t)n_act * kNniSums * (n_blk + nB) * sizeof(double)))) return rc;
+  // the request in one copy from pinned memory (the pass before has been waited for)
+  const size_t off_idx = (size_t)n_act * 2 * sizeof(double), off_model = off_idx + (size_t)n_act * sizeof(int32_t);
+  std::memcpy(h->h_nni, t, off_idx);
+  std::memcpy(h->h_nni + off_idx, idx, (size_t)n_act * sizeof(int32_t));
+  std::memcpy(h->h_nni + off_model, model, (size_t)n_act * sizeof(int32_t));
+  HIPCHK(h, hipMemcpyAsync(h->d_nni + st.req, h->h_nni, NniStage::req_bytes(n_act), hipMemcpyHostToDevice, h->stream));
+  NniEvalArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.coef = (const double*)h->post_buf;
+  a.weights = h->weights;
+  a.idx = reinterpret_cast<const int32_t*>(h->d_nni + st.req + off_idx);
+  a.model = reinterpret_cast<const int32_t*>(h->d_nni + st.req + off_model);
+  a.t = reinterpret_cast<const double*>(h->d_nni + st.req);
+  a.rates = h->rates;
+  a.lambda = h->lambda;
+  a.ex = reinterpret_cast<double*>(h->d_nni + st.ex);
+  a.blk = h->map_blk;
+  a.n_pad = h->n_pad;
+  a.n_patterns = h->n_patterns;
+  a.S = S;
+  a.C = C;
+  a.n_blk = n_blk;
+  a.n_act = n_act;
+  nni_expo_kernel<<<(unsigned)((n_act * CS + 63) / 64), 64, 0, h->stream>>>(a);
+  HIPCHK(h, hipGetLastError());
+  {
+    TimedSpan span(h, PLK_TIME_ROOT, 2);
+    nni_eval_kernel<<<dim3((unsigned)n_blk, (unsigned)n_act), kNniThreads, 0, h->stream>>>(a);
+    HIPCHK(h, hipGetLastError());
+    span.stop();
+  }
+  double* d_out = h->map_blk + (size_t)n_act * kNniSums * n_blk;
+  map_blocks_kernel<<<(unsigned)((n_act * kNniSums * nB + 255) / 256), 256, 0, h->stream>>>(h->map_blk, d_out, n_act * kNniSums, n_blk, per, nB);
+  HIPCHK(h, hipGetLastError());
+  const double* hbuf = reinterpret_cast<const double*>(h->h_nni + NniStage::req_bytes(chunk));
+  HIPCHK(h, hipMemcpyAsync(const_cast<double*>(hbuf), d_out, (size_t)n_act * kNniSums * nB * sizeof(double),
+                           hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  for (int r = 0; r < n_act * kNniSums; ++r)
+    std::copy(hbuf + (size_t)r * nB, hbuf + (size_t)(r + 1) * nB, blocks + (size_t)r * nB_total + B0);
+  return PLK_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -5121,6 +5361,126 @@ int plk_branch_counts(plk_handle h, int n_branches, const int32_t* branches, dou
       for (int64_t B = 0; B < nB; ++B) s += blocks[r * nB + B];
       totals[r] = s;
     }
+  return PLK_OK;
+}
+
+int plk_nni_scores(plk_handle h, int n_moves, const int32_t* son, const int32_t* uncle, const int32_t* model,
+                   const double* t0, double t_min, double t_max, double tol, int max_iter, double* t_opt, double* delta,
+                   double* d1, double* d2, int32_t* status) {
+  env_refresh();
+  if (!h) return fail(h, PLK_ERR_ARG, "null handle");
+  if (n_moves <= 0 || !son || !uncle) return fail(h, PLK_ERR_ARG, "bad move list (%d moves)", n_moves);
+  if (!t0 || !t_opt || !delta) return fail(h, PLK_ERR_ARG, "t0, t_opt and delta are required");
+  if (!(t_min > 0.0) || !(t_max >= t_min) || !(tol >= 0.0) || max_iter < 0)
+    return fail(h, PLK_ERR_ARG, "bad bounds [%g, %g], tolerance %g or budget %d", t_min, t_max, tol, max_iter);
+  for (int i = 0; i < n_moves; ++i)
+    if (!(t0[i] >= t_min && t0[i] <= t_max))
+      return fail(h, PLK_ERR_ARG, "move %d: t0 = %g outside [%g, %g]", i, t0[i], t_min, t_max);
+  const bool multi = !h->shards.empty();
+  plk_handle x0 = multi ? h->shards[0] : h;
+  std::vector<NniMove> recs;
+  int rc = nni_plan(x0, n_moves, son, uncle, model, recs);
+  if (rc) return multi ? multi_forward(h, rc) : rc;
+  auto each = [&](const std::function<int(plk_handle, int64_t)>& f) { return multi ? multi_slices(h, f) : f(h, 0); };
+  const int CS = x0->C * x0->S;
+  int64_t n_pad = x0->n_pad;
+  for (plk_handle s : h->shards) n_pad = std::max(n_pad, s->n_pad);
+  // the staging of a chunk of moves stays under kNniStageCap (PLK_TUNE NNI_CAP_KB: a smaller cap)
+  const size_t cap = (size_t)tune_int("NNI_CAP_KB", (int)(kNniStageCap >> 10), 1, (int)(kNniStageCap >> 10)) << 10;
+  const size_t per_move = (size_t)(CS + kNniExtra) * n_pad * sizeof(double);
+  const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_moves, cap / per_move));
+  // block sums of every shard at their global block index, added in that order: the root
+  // reduction's rule, so no Newton decision depends on the sharding
+  const int64_t nB = (h->n_patterns + kRootBlock - 1) / kRootBlock;
+  std::vector<double> blocks;
+  h->nni_passes = 0;
+  for (int n0 = 0; n0 < n_moves; n0 += chunk) {
+    const int cn = std::min(chunk, n_moves - n0);
+    if ((rc = each([&](plk_handle x, int64_t) { return nni_build_local(x, recs.data() + n0, cn, chunk, n0 == 0); }))) return rc;
+    std::vector<int32_t> act((size_t)cn), mdl;
+    std::vector<double> tt, val, acc_t;  // acc_t: the length of every move's last accepted point
+    // F, d1, d2 of the moves act[] at the lengths tt[], and F(tt) - F(accepted point)
+    auto evaluate = [&]() -> int {
+      const int n_act = (int)act.size();
+      mdl.resize(act.size());
+      for (int i = 0; i < n_act; ++i) mdl[(size_t)i] = recs[(size_t)(n0 + act[(size_t)i])].model;
+      tt.resize(2 * act.size());
+      for (int i = 0; i < n_act; ++i) tt[(size_t)(n_act + i)] = acc_t[(size_t)act[(size_t)i]];
+      blocks.assign((size_t)n_act * kNniSums * nB, 0.0);
+      const int r = each([&](plk_handle x, int64_t a) {
+        return nni_eval_local(x, chunk, n_act, act.data(), mdl.data(), tt.data(), blocks.data(), nB, a / kRootBlock);
+      });
+      if (r) return r;
+      val.assign((size_t)n_act * kNniSums, 0.0);
+      for (size_t q = 0; q < val.size(); ++q) {
+        double s = 0.0;
+        for (int64_t B = 0; B < nB; ++B) s += blocks[q * nB + B];
+        val[q] = s;
+      }
+      h->nni_passes++;
+      return PLK_OK;
+    };
+    for (int i = 0; i < cn; ++i) act[(size_t)i] = i;
+    tt.assign(t0 + n0, t0 + n0 + cn);
+    acc_t = tt;
+    if ((rc = evaluate())) return rc;
+    // the last accepted point of every move, and the pending trial
+    std::vector<double>& pt = acc_t;
+    std::vector<double> F((size_t)cn), D1((size_t)cn), D2((size_t)cn), trial((size_t)cn, 0.0);
+    std::vector<char> half((size_t)cn, 0);
+    std::vector<int32_t> st((size_t)cn, 0);
+    for (int i = 0; i < cn; ++i) F[(size_t)i] = val[kNniSums * (size_t)i], D1[(size_t)i] = val[kNniSums * (size_t)i + 1], D2[(size_t)i] = val[kNniSums * (size_t)i + 2];
+    for (int it = 0; max_iter > 0;) {
+      std::vector<int32_t> next;
+      tt.clear();
+      for (int32_t i : act) {
+        const double t = pt[(size_t)i];
+        double tp = half[(size_t)i] ? 0.5 * (t + trial[(size_t)i])
+                    : D2[(size_t)i] < 0.0 ? t - D1[(size_t)i] / D2[(size_t)i]
+                    : D1[(size_t)i] > 0.0 ? 2.0 * t
+                                          : 0.5 * t;
+        tp = tp != tp ? t : std::min(std::max(tp, t_min), t_max);
+        if (std::fabs(tp - t) <= tol * std::max(t, t_min)) continue;  // converged: drops out
+        trial[(size_t)i] = tp;
+        next.push_back(i);
+        tt.push_back(tp);
+      }
+      act.swap(next);
+      if (act.empty()) break;
+      if (it == max_iter) {
+        for (int32_t i : act) st[(size_t)i] = 1;
+        break;
+      }
+      if ((rc = evaluate())) return rc;
+      ++it;
+      for (size_t k = 0; k < act.size(); ++k) {
+        const size_t i = (size_t)act[k];
+        // F(t') >= F(t), decided on the change formed per pattern: the two sums of logs agree to
+        // more digits than they carry once the steps are short.  F moves by that change, so it
+        // never falls
+        const double dF = val[kNniSums * k + 3];
+        if (dF >= 0.0) {
+          pt[i] = trial[i], F[i] += dF, D1[i] = val[kNniSums * k + 1], D2[i] = val[kNniSums * k + 2];
+          half[i] = 0;
+        } else {
+          half[i] = 1;
+        }
+      }
+    }
+    for (int i = 0; i < cn; ++i) {
+      t_opt[n0 + i] = pt[(size_t)i];
+      delta[n0 + i] = F[(size_t)i];
+      if (d1) d1[n0 + i] = D1[(size_t)i];
+      if (d2) d2[n0 + i] = D2[(size_t)i];
+      if (status) status[n0 + i] = st[(size_t)i];
+    }
+  }
+  return PLK_OK;
+}
+
+int plk_nni_passes(plk_handle h, int64_t* passes) {
+  if (!h || !passes) return fail(h, PLK_ERR_ARG, "null argument");
+  *passes = h->nni_passes;
   return PLK_OK;
 }
 

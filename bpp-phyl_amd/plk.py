@@ -41,7 +41,7 @@ EXPORTS = [
     "plk_root_underflow", "plk_exchange_stride", "plk_exchange_pack", "plk_exchange_reduce",
     "plk_exchange_rank_sums", "plk_clock_records", "plk_clock_waves", "plk_clock_wave_tails",
     "plk_node_posteriors", "plk_set_count_types", "plk_update_count_matrices", "plk_set_count_matrix",
-    "plk_get_count_matrix", "plk_branch_counts",
+    "plk_get_count_matrix", "plk_branch_counts", "plk_nni_scores", "plk_nni_passes",
 ]
 
 
@@ -136,6 +136,9 @@ def load(path: str = LIB_PATH) -> ct.CDLL:
         "plk_set_count_matrix": ([ct.c_void_p, ct.c_int, ct.c_int, dp], ct.c_int),
         "plk_get_count_matrix": ([ct.c_void_p, ct.c_int, dp], ct.c_int),
         "plk_branch_counts": ([ct.c_void_p, ct.c_int, ip, dp, dp], ct.c_int),
+        "plk_nni_scores": ([ct.c_void_p, ct.c_int, ip, ip, ip, dp, ct.c_double, ct.c_double, ct.c_double, ct.c_int,
+                            dp, dp, dp, dp, ip], ct.c_int),
+        "plk_nni_passes": ([ct.c_void_p, P(ct.c_int64)], ct.c_int),
         "plk_kernel_path": ([ct.c_void_p], ct.c_char_p),
         "plk_compressed_work": ([ct.c_void_p, P(ct.c_int64)], ct.c_int),
         "plk_evaluate": ([ct.c_void_p, ct.c_int, ip, ip, dp, P(plk_op), ct.c_int, ct.c_int, dp, dp], ct.c_int),
@@ -532,6 +535,36 @@ class Engine:
         self._chk(self.lib.plk_branch_counts(
             self.h, n, br.ctypes.data_as(ct.POINTER(ct.c_int32)),
             _d(out["counts"]) if counts else None, _d(out["totals"]) if totals else None))
+        return out
+
+    def nni_scores(self, son, uncle, t0, t_min: float = 1e-6, t_max: float = 100.0, tol: float = 1e-8,
+                   max_iter: int = 0, model=None) -> dict:
+        """plk_nni_scores for the moves (son, uncle) of the last traversal's tree, branch p =
+        father(son) starting at length t0: a dict with "t_opt", "delta" (lnL of the swapped tree at
+        t_opt minus the current lnL), "d1", "d2" (its derivatives in t there), "status" (0 converged,
+        1 budget spent) per move, and "passes", the evaluation passes the call took.  max_iter = 0
+        evaluates at t0 only."""
+        s = np.ascontiguousarray(son, dtype=np.int32).ravel()
+        u = np.ascontiguousarray(uncle, dtype=np.int32).ravel()
+        t = np.ascontiguousarray(t0, dtype=np.float64).ravel()
+        n = len(s)
+        if len(u) != n or len(t) != n:
+            raise ValueError("son, uncle and t0 must have one entry per move")
+        ip = ct.POINTER(ct.c_int32)
+        mp = None
+        if model is not None:
+            m = np.ascontiguousarray(model, dtype=np.int32).ravel()
+            if len(m) != n:
+                raise ValueError("model must have one entry per move")
+            mp = m.ctypes.data_as(ip)
+        out = {k: np.empty(n) for k in ("t_opt", "delta", "d1", "d2")}
+        out["status"] = np.empty(n, dtype=np.int32)
+        self._chk(self.lib.plk_nni_scores(
+            self.h, n, s.ctypes.data_as(ip), u.ctypes.data_as(ip), mp, _d(t), t_min, t_max, tol, max_iter,
+            _d(out["t_opt"]), _d(out["delta"]), _d(out["d1"]), _d(out["d2"]), out["status"].ctypes.data_as(ip)))
+        passes = ct.c_int64(0)
+        self._chk(self.lib.plk_nni_passes(self.h, ct.byref(passes)))
+        out["passes"] = passes.value
         return out
 
     def set_timing(self, on: bool):

@@ -404,6 +404,71 @@ int plk_branch_counts(plk_handle h, int n_branches, const int32_t* branches,
                       double* counts /* n_branches x n_patterns x T, or NULL */,
                       double* totals /* n_branches x T, or NULL */);
 
+/* Nearest-neighbour interchanges of the last plk_update_partials tree, scored with the length of
+ * the move's branch re-estimated.  A move is (son s, uncle u): p is the father of s, g the father
+ * of p and u another son of g; s and u change places and branch p gets the length t.  Per
+ * pattern and class, with q_v = P_v L_v (a tip: its code row), up_g = pi at the root and else
+ * sum_y u_g[y] P_g[y][x] with u_g = U_g (pi folded in as in plk_node_posteriors),
+ *   A1 = up_g q_s prod_{o son of g, o not p, u} q_o,   A2 = q_u prod_{o son of p, o not s} q_o,
+ *   B1 = up_g q_u prod_o q_o,  B2 = q_s prod_o q_o,    l_cur = sum_c p_c B1^T P_p B2,
+ * and with the real eigen system (V, Vinv, lambda) of `model` (that of branch p),
+ *   gamma[c][k] = p_c (A1^T V)[k] (Vinv A2)[k] / l_cur,
+ *   rho(t)   = sum_c sum_k gamma[c][k] exp(lambda_k r_c t),
+ *   delta(t) = sum_p w_p log rho(t) = lnL(swapped tree, branch p of length t) - lnL(current tree),
+ *   d1 = sum_p w_p rho'/rho,   d2 = sum_p w_p (rho''/rho - (rho'/rho)^2).
+ * l_cur and gamma come from the same stored vectors, so scale counts cancel and are never read.
+ * The matrix-vector products are paid once per move; every trial length is one streaming pass
+ * over C S + 2 coefficients per pattern.  While t max|lambda_k r_c| <= 1, rho is summed as
+ * d + sum gamma expm1(lambda r t) with d = sum_c p_c A1 . A2 / l_cur = sum gamma, which is formed
+ * without a subtraction: where the two sides of a move disagree rho is small against the gamma
+ * it is summed from, and at t = 1e-6 the plain sum lost six digits of d1 on 20 states.
+ *
+ * max_iter == 0: every move is evaluated at t0 (t_opt = t0; status 0).  max_iter > 0: a
+ * safeguarded Newton ascent, all moves in lockstep, at most max_iter evaluation passes after the
+ * first.  From a point (t, F, d1, d2) the proposal is t' = t - d1 / d2 when d2 < 0, else 2 t when
+ * d1 > 0, else t / 2, clamped to [t_min, t_max]; after a rejected trial it is the midpoint of t
+ * and that trial.  A move is converged when |t' - t| <= tol max(t, t_min) and then drops out of
+ * the later passes; otherwise t' is evaluated and accepted when F(t') >= F(t).  That comparison
+ * is taken on F(t') - F(t) = sum_p w_p log1p((rho(t') - rho(t)) / rho(t)), summed per pattern in
+ * the same pass from rho(t') - rho(t) = sum gamma exp(lambda r t) expm1(lambda r (t' - t)): near
+ * the optimum a step changes F by less than the rounding of F itself, and the difference of two
+ * sums of logs would let rounding decide.  t_opt, d1 and d2 are those of the last accepted
+ * point and delta is delta(t0) plus the accepted changes, so delta >= delta(t0) and delta is
+ * delta(t_opt) (to rounding).
+ * status: 0 converged, 1 iteration budget spent.  t0 is required: the engine stores P(t), not t.
+ * The three sums are formed per plk_block_size() patterns on the device in fixed order and over
+ * the blocks in pattern order on the host (the root reduction's rule), and every decision is
+ * taken on them, so no result depends on sharding.
+ *
+ * Replaces NNIHomogeneousTreeLikelihood::testNNI (Likelihood/NNIHomogeneousTreeLikelihood.cpp:
+ * 205-309) and its BranchLikelihood (:93-120), for every move of a round of NNITopologySearch
+ * (NNITopologySearch.cpp:97-212) at once.  Deviations:
+ *   - Newton to `tol` in the place of Brent at tolerance 0.1: t_opt is closer to the optimum and
+ *     delta at least as large.  The reference returns -delta.
+ *   - A pattern whose l_cur or rho is not a positive finite number (an unscaled underflow) adds 0
+ *     to all three sums and raises no error, as posteriors and mapping have it.
+ *   - Real eigen systems only; p and g of at most three sons.
+ * PLK_ERR_STATE without PLK_FLAG_DOUBLE_RECURSIVE, before a traversal, without dP / d2P (the
+ * preorder pass demands them) or for a model without an eigen system; PLK_ERR_UNSUPPORTED with
+ * PLK_FLAG_SUBTREE_PATTERNS, under a communicator, or when p or g has more than three sons;
+ * PLK_ERR_ARG when s is the root or a son of the root, u is not a son of g other than p, an index
+ * is out of range or outside the current tree, n_moves <= 0, t_min <= 0, t_max < t_min or a t0
+ * outside the bounds.  The preorder pass runs only if a P(t), partial, tip code, pi or rate has
+ * changed since the last one; the call changes no partial, U, P(t), plk_kernel_path or the next
+ * plk_root_loglik.  Device staging of the coefficients is bounded (2 GiB): longer move lists
+ * run in chunks, each built and then optimised.  A multi-device handle builds and evaluates
+ * shard by shard and the parent drives the Newton loop over the block sums in global block order
+ * (bitwise the single-device result). */
+int plk_nni_scores(plk_handle h, int n_moves, const int32_t* son, const int32_t* uncle,
+                   const int32_t* model /* n_moves, or NULL: model 0 */,
+                   const double* t0 /* n_moves */,
+                   double t_min, double t_max, double tol, int max_iter,
+                   double* t_opt, double* delta, double* d1, double* d2 /* each n_moves; d1, d2 nullable */,
+                   int32_t* status /* n_moves, nullable */);
+/* Evaluation passes of the last plk_nni_scores on this handle (the first pass of every chunk
+ * included). */
+int plk_nni_passes(plk_handle h, int64_t* passes);
+
 /* Instrumentation: HIP-event timing on the handle's stream of the kernels selected
  * by the mask given to plk_set_timing (0 = off).  Each timed launch adds an event
  * pair to the stream, so time only what is needed. */
