@@ -16,6 +16,7 @@
 #include "plk_post.hpp"
 #include "plk_map.hpp"
 #include "plk_nni.hpp"
+#include "plk_pair.hpp"
 #include "plk_exchange.hpp"
 
 #include <hip/hip_runtime.h>
@@ -420,6 +421,11 @@ struct plk_handle_s {
   char* h_nni = nullptr;                // pinned: a pass's request and its block sums
   size_t h_nni_cap = 0;
   int64_t nni_passes = 0;               // evaluation passes of the last plk_nni_scores (plk_nni_passes)
+  // pairwise distances (plk_pair.hpp): the per-block tables of a chunk of pairs live in post_buf,
+  // everything else of the chunk (summed tables, basis, request, results) in d_pair
+  char* d_pair = nullptr;
+  size_t d_pair_cap = 0;
+  int64_t pair_passes = 0;              // evaluation passes of the slowest pair, last plk_pair_distances
   // multi-device handle (plk_create_multi): one shard handle per device over contiguous,
   // block-aligned pattern ranges; the parent owns no device memory
   std::vector<plk_handle> shards;
@@ -1221,7 +1227,7 @@ int plk_destroy(plk_handle h) {
                   h->d2_sums, h->d_dprog, h->pmatsT, h->d_ucodes, h->d_units, h->d_cherry3,
                   h->d_cherry_tips, h->d_cherry, h->d_drb, h->d_drm, h->dr_blk, h->dr_out, h->d_drpre, h->d_sbctr,
                   h->d_cherry_rows, h->d_kidsl, h->d_cls, h->d_ucodes_dc, h->d_units_start, h->d_post, h->post_buf,
-                  h->count_G, h->wmats, h->d_mapb, h->map_blk, h->d_mapreq, h->d_nni, h->nni_vit};
+                  h->count_G, h->wmats, h->d_mapb, h->map_blk, h->d_mapreq, h->d_nni, h->nni_vit, h->d_pair};
   for (void* p : bufs)
     if (p) hipFree(p);
   if (h->h_req) (void)hipHostFree(h->h_req);
@@ -4503,6 +4509,209 @@ int nni_eval_local(plk_handle h, int chunk, int n_act, const int32_t* idx, const
 }
 }  // namespace
 
+// ---------------------------------------------------------------------------
+// Pairwise distances (plk_pair.hpp): "count a chunk of pairs" per handle (a shard counts its own
+// patterns), then basis and Newton on one handle from the summed tables.
+// ---------------------------------------------------------------------------
+namespace {
+// Byte offsets into d_pair for chunks of up to `chunk` pairs over Ut table codes.
+struct PairStage {
+  size_t full, table, alpha, beta, delta, t0, out, tip_a, tip_b, orig, res, status, passes, bytes;
+  PairStage(int chunk, int Ut, int S) {
+    size_t o = 0;
+    auto take = [&](size_t n) {
+      const size_t r = o;
+      o += (n + 15) & ~(size_t)15;
+      return r;
+    };
+    full = take((size_t)chunk * Ut * Ut * sizeof(double));
+    table = take((size_t)Ut * S * sizeof(double));
+    alpha = take((size_t)Ut * S * sizeof(double));
+    beta = take((size_t)Ut * S * sizeof(double));
+    delta = take((size_t)Ut * Ut * sizeof(double));
+    t0 = take((size_t)chunk * sizeof(double));
+    out = take((size_t)chunk * 4 * sizeof(double));
+    tip_a = take((size_t)chunk * sizeof(int32_t));
+    tip_b = take((size_t)chunk * sizeof(int32_t));
+    orig = take(256 * sizeof(int32_t));
+    res = take((size_t)Ut * sizeof(int32_t));
+    status = take((size_t)chunk * sizeof(int32_t));
+    passes = take((size_t)chunk * sizeof(int32_t));
+    bytes = o;
+  }
+};
+
+// The argument and state checks both entry points share (h: the handle the caller holds).
+int pair_check(plk_handle h, int n_pairs, const int32_t* tip_a, const int32_t* tip_b) {
+  if (n_pairs <= 0 || !tip_a || !tip_b) return fail(h, PLK_ERR_ARG, "bad pair list (%d pairs)", n_pairs);
+  for (int i = 0; i < n_pairs; ++i) {
+    if (tip_a[i] < 0 || tip_a[i] >= h->n_tips || tip_b[i] < 0 || tip_b[i] >= h->n_tips)
+      return fail(h, PLK_ERR_ARG, "pair %d: (%d, %d) outside [0, %d)", i, tip_a[i], tip_b[i], h->n_tips);
+    if (tip_a[i] == tip_b[i]) return fail(h, PLK_ERR_ARG, "pair %d: tip %d with itself", i, tip_a[i]);
+  }
+  if (h->comm) return fail(h, PLK_ERR_UNSUPPORTED, "pairwise counts under a communicator");
+  std::vector<plk_handle> one(1, h);
+  for (plk_handle x : h->shards.empty() ? one : h->shards) {
+    if (!x->table_set) return fail(h, PLK_ERR_STATE, "plk_set_code_table must precede the pairwise calls");
+    for (int i = 0; i < n_pairs; ++i)
+      for (int t : {tip_a[i], tip_b[i]})
+        if (!x->tip_set[t]) return fail(h, PLK_ERR_STATE, "pair %d: tip %d has no codes yet", i, t);
+    if (x->n_codes > kPairMaxCodes)
+      return fail(h, PLK_ERR_UNSUPPORTED, "%d codes in use; the pairwise tables hold at most %d", x->n_codes, kPairMaxCodes);
+  }
+  return PLK_OK;
+}
+
+// Pairs per chunk: the per-block tables of a chunk stay under kPostStageCap (PLK_TUNE PAIR_CAP_KB:
+// a smaller cap) on every shard.
+int pair_chunk(plk_handle h, int n_pairs) {
+  std::vector<plk_handle> one(1, h);
+  const std::vector<plk_handle>& xs = h->shards.empty() ? one : h->shards;
+  const size_t Ut = (size_t)xs[0]->n_codes_table;
+  size_t per = 0;
+  for (plk_handle x : xs) per = std::max(per, (size_t)x->n_blocks * x->n_codes * x->n_codes);
+  per = (per + Ut * Ut) * sizeof(double);
+  const size_t cap = (size_t)tune_int("PAIR_CAP_KB", (int)(kPostStageCap >> 10), 1, (int)(kPostStageCap >> 10)) << 10;
+  const size_t most = (size_t)kPairGroup * 65535;  // grid.y of pair_count_kernel
+  return (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>((size_t)n_pairs, most), cap / per));
+}
+
+int pair_prepare(plk_handle h, int chunk) {
+  hipSetDevice(h->device);
+  const int U = h->n_codes;
+  const PairStage st(chunk, h->n_codes_table, h->S);
+  int rc;
+  if ((rc = ensure_cap(h, (void**)&h->post_buf, &h->post_buf_cap, (size_t)chunk * h->n_blocks * U * U * sizeof(double)))) return rc;
+  if ((rc = ensure_cap(h, (void**)&h->d_pair, &h->d_pair_cap, st.bytes))) return rc;
+  std::vector<int32_t> orig(h->code_orig.begin(), h->code_orig.end());
+  HIPCHK(h, hipMemcpyAsync(h->d_pair + st.orig, orig.data(), orig.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));  // orig is a local
+  return PLK_OK;
+}
+
+// The tables [cn][Ut][Ut] of the pairs (tip_a[i], tip_b[i]) over this handle's patterns, into
+// d_pair (caller's code numbering); to `host` too when given.
+int pair_count_local(plk_handle h, int chunk, int cn, const int32_t* tip_a, const int32_t* tip_b, double* host) {
+  hipSetDevice(h->device);
+  const int U = h->n_codes, Ut = h->n_codes_table;
+  const PairStage st(chunk, Ut, h->S);
+  HIPCHK(h, hipMemcpyAsync(h->d_pair + st.tip_a, tip_a, (size_t)cn * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(h->d_pair + st.tip_b, tip_b, (size_t)cn * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+  double* full = reinterpret_cast<double*>(h->d_pair + st.full);
+  HIPCHK(h, hipMemsetAsync(full, 0, (size_t)cn * Ut * Ut * sizeof(double), h->stream));
+  PairCountArgs a;
+  a.codes = h->codes;
+  a.weights = h->weights;
+  a.tip_a = reinterpret_cast<const int32_t*>(h->d_pair + st.tip_a);
+  a.tip_b = reinterpret_cast<const int32_t*>(h->d_pair + st.tip_b);
+  a.part = reinterpret_cast<double*>(h->post_buf);
+  a.n_pad = h->n_pad;
+  a.n_patterns = h->n_patterns;
+  a.U = U;
+  a.n_pairs = cn;
+  const size_t lds = ((U <= kPairStageW ? (size_t)kPairBlock : 0) + (size_t)(U <= kPairOwnBins ? kPairThreads / 64 : 1) * U * U) * sizeof(double);
+  {
+    TimedSpan span(h, PLK_TIME_TABLES, 3);
+    pair_count_kernel<<<dim3((unsigned)h->n_blocks, (unsigned)((cn + kPairGroup - 1) / kPairGroup)), kPairThreads, lds, h->stream>>>(a);
+    HIPCHK(h, hipGetLastError());
+    pair_sum_kernel<<<(unsigned)(((int64_t)cn * U * U + 255) / 256), 256, 0, h->stream>>>(
+        a.part, full, reinterpret_cast<const int32_t*>(h->d_pair + st.orig), h->n_blocks, cn, U, Ut);
+    HIPCHK(h, hipGetLastError());
+    if (span.stop()) h->n_table_launches += 2;
+  }
+  if (host) HIPCHK(h, hipMemcpyAsync(host, full, (size_t)cn * Ut * Ut * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));  // the pair lists are the caller's
+  return PLK_OK;
+}
+
+int pair_basis_local(plk_handle h, int chunk, int model) {
+  hipSetDevice(h->device);
+  const int S = h->S, Ut = h->n_codes_table;
+  const PairStage st(chunk, Ut, S);
+  HIPCHK(h, hipMemcpyAsync(h->d_pair + st.table, h->code_table_host.data(), (size_t)Ut * S * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  PairBasisArgs a;
+  a.table = reinterpret_cast<const double*>(h->d_pair + st.table);
+  a.V = h->V + (size_t)model * S * S;
+  a.Vinv = h->Vinv + (size_t)model * S * S;
+  a.pi = h->pi;
+  a.alpha = reinterpret_cast<double*>(h->d_pair + st.alpha);
+  a.beta = reinterpret_cast<double*>(h->d_pair + st.beta);
+  a.delta = reinterpret_cast<double*>(h->d_pair + st.delta);
+  a.res = reinterpret_cast<int32_t*>(h->d_pair + st.res);
+  a.S = S;
+  a.Ut = Ut;
+  pair_basis_kernel<<<(unsigned)std::min(64, (Ut * std::max(S, Ut) + 255) / 256), 256, 0, h->stream>>>(a);
+  HIPCHK(h, hipGetLastError());
+  return PLK_OK;
+}
+
+// The ascent of the chunk's pairs from the tables in d_pair (`full_host`: uploaded first).
+int pair_newton_local(plk_handle h, int chunk, int cn, int model, const double* full_host, const double* t0, double t_min,
+                      double t_max, double tol, int max_iter, double* t_opt, double* lnl, double* d1, double* d2,
+                      int32_t* status, int64_t* passes) {
+  hipSetDevice(h->device);
+  const int S = h->S, Ut = h->n_codes_table;
+  const PairStage st(chunk, Ut, S);
+  if (full_host)
+    HIPCHK(h, hipMemcpyAsync(h->d_pair + st.full, full_host, (size_t)cn * Ut * Ut * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  if (t0) HIPCHK(h, hipMemcpyAsync(h->d_pair + st.t0, t0, (size_t)cn * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  PairNewtonArgs a;
+  a.full = reinterpret_cast<const double*>(h->d_pair + st.full);
+  a.alpha = reinterpret_cast<const double*>(h->d_pair + st.alpha);
+  a.beta = reinterpret_cast<const double*>(h->d_pair + st.beta);
+  a.delta = reinterpret_cast<const double*>(h->d_pair + st.delta);
+  a.res = reinterpret_cast<const int32_t*>(h->d_pair + st.res);
+  a.lambda = h->lambda + (size_t)model * S;
+  a.rates = h->rates;
+  a.probs = h->probs;
+  a.t0 = t0 ? reinterpret_cast<const double*>(h->d_pair + st.t0) : nullptr;
+  a.out = reinterpret_cast<double*>(h->d_pair + st.out);
+  a.status = reinterpret_cast<int32_t*>(h->d_pair + st.status);
+  a.passes = reinterpret_cast<int32_t*>(h->d_pair + st.passes);
+  a.t_min = t_min;
+  a.t_max = t_max;
+  a.tol = tol;
+  a.S = S;
+  a.C = h->C;
+  a.Ut = Ut;
+  a.max_iter = max_iter;
+  {
+    TimedSpan span(h, PLK_TIME_ROOT, 2);
+    pair_newton_kernel<<<(unsigned)cn, kPairThreads, (size_t)(5 * S + 4 * (kPairThreads / 64)) * sizeof(double), h->stream>>>(a);
+    HIPCHK(h, hipGetLastError());
+    span.stop();
+  }
+  std::vector<double> out((size_t)cn * 4);
+  std::vector<int32_t> sp((size_t)cn * 2);
+  HIPCHK(h, hipMemcpyAsync(out.data(), a.out, out.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(sp.data(), a.status, (size_t)cn * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(sp.data() + cn, a.passes, (size_t)cn * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  for (int i = 0; i < cn; ++i) {
+    t_opt[i] = out[4 * (size_t)i];
+    lnl[i] = out[4 * (size_t)i + 1];
+    if (d1) d1[i] = out[4 * (size_t)i + 2];
+    if (d2) d2[i] = out[4 * (size_t)i + 3];
+    if (status) status[i] = sp[(size_t)i];
+    *passes = std::max<int64_t>(*passes, sp[(size_t)(cn + i)]);
+  }
+  return PLK_OK;
+}
+
+// A chunk's tables on a multi-device handle: every shard counts its own patterns, the parent
+// adds the tables in shard order (exact for integer weights).
+int pair_count_multi(plk_handle h, int chunk, int cn, const int32_t* tip_a, const int32_t* tip_b, double* sum) {
+  const size_t n = (size_t)cn * h->shards[0]->n_codes_table * h->shards[0]->n_codes_table, ns = h->shards.size();
+  std::vector<double> buf(ns * n);
+  const int rc = multi_run(h, [&](size_t i) { return pair_count_local(h->shards[i], chunk, cn, tip_a, tip_b, buf.data() + i * n); });
+  if (rc) return rc;
+  std::copy(buf.begin(), buf.begin() + n, sum);
+  for (size_t i = 1; i < ns; ++i)
+    for (size_t e = 0; e < n; ++e) sum[e] += buf[i * n + e];
+  return PLK_OK;
+}
+}  // namespace
+
 extern "C" {
 
 int plk_update_partials(plk_handle h, const plk_op* ops, int n_ops) {
@@ -5481,6 +5690,71 @@ int plk_nni_scores(plk_handle h, int n_moves, const int32_t* son, const int32_t*
 int plk_nni_passes(plk_handle h, int64_t* passes) {
   if (!h || !passes) return fail(h, PLK_ERR_ARG, "null argument");
   *passes = h->nni_passes;
+  return PLK_OK;
+}
+
+int plk_pair_counts(plk_handle h, int n_pairs, const int32_t* tip_a, const int32_t* tip_b, double* counts) {
+  env_refresh();
+  if (!h || !counts) return fail(h, PLK_ERR_ARG, "null argument");
+  int rc = pair_check(h, n_pairs, tip_a, tip_b);
+  if (rc) return rc;
+  const bool multi = !h->shards.empty();
+  const int chunk = pair_chunk(h, n_pairs);
+  if ((rc = multi ? multi_each(h, [&](plk_handle x) { return pair_prepare(x, chunk); }) : pair_prepare(h, chunk))) return rc;
+  const size_t Ut = (size_t)(multi ? h->shards[0] : h)->n_codes_table;
+  for (int n0 = 0; n0 < n_pairs; n0 += chunk) {
+    const int cn = std::min(chunk, n_pairs - n0);
+    double* dst = counts + (size_t)n0 * Ut * Ut;
+    if ((rc = multi ? pair_count_multi(h, chunk, cn, tip_a + n0, tip_b + n0, dst)
+                    : pair_count_local(h, chunk, cn, tip_a + n0, tip_b + n0, dst)))
+      return rc;
+  }
+  return PLK_OK;
+}
+
+int plk_pair_distances(plk_handle h, int n_pairs, const int32_t* tip_a, const int32_t* tip_b, int model, const double* t0,
+                       double t_min, double t_max, double tol, int max_iter, double* t_opt, double* lnl, double* d1,
+                       double* d2, int32_t* status) {
+  env_refresh();
+  if (!h || !t_opt || !lnl) return fail(h, PLK_ERR_ARG, "t_opt and lnl are required");
+  if (!(t_min > 0.0) || !(t_max >= t_min) || !(tol >= 0.0) || max_iter < 0)
+    return fail(h, PLK_ERR_ARG, "bad bounds [%g, %g], tolerance %g or budget %d", t_min, t_max, tol, max_iter);
+  if (model < 0 || model >= h->n_models) return fail(h, PLK_ERR_ARG, "model %d out of range", model);
+  int rc = pair_check(h, n_pairs, tip_a, tip_b);
+  if (rc) return rc;
+  if (t0)
+    for (int i = 0; i < n_pairs; ++i)
+      if (!(t0[i] >= t_min && t0[i] <= t_max))
+        return fail(h, PLK_ERR_ARG, "pair %d: t0 = %g outside [%g, %g]", i, t0[i], t_min, t_max);
+  const bool multi = !h->shards.empty();
+  plk_handle x0 = multi ? h->shards[0] : h;
+  if (!x0->rates_set || !x0->pi_set) return fail(h, PLK_ERR_STATE, "rates and root frequencies must be set");
+  if (!x0->eigen_set[model]) return fail(h, PLK_ERR_STATE, "model %d has no eigen system", model);
+  const int chunk = pair_chunk(h, n_pairs);
+  if ((rc = multi ? multi_each(h, [&](plk_handle x) { return pair_prepare(x, chunk); }) : pair_prepare(h, chunk))) return rc;
+  if ((rc = pair_basis_local(x0, chunk, model))) return multi ? multi_forward(h, rc) : rc;
+  const size_t Ut = (size_t)x0->n_codes_table;
+  std::vector<double> sum;
+  h->pair_passes = 0;
+  for (int n0 = 0; n0 < n_pairs; n0 += chunk) {
+    const int cn = std::min(chunk, n_pairs - n0);
+    if (multi) {
+      sum.resize((size_t)cn * Ut * Ut);
+      if ((rc = pair_count_multi(h, chunk, cn, tip_a + n0, tip_b + n0, sum.data()))) return rc;
+    } else if ((rc = pair_count_local(h, chunk, cn, tip_a + n0, tip_b + n0, nullptr))) {
+      return rc;
+    }
+    rc = pair_newton_local(x0, chunk, cn, model, multi ? sum.data() : nullptr, t0 ? t0 + n0 : nullptr, t_min, t_max, tol,
+                           max_iter, t_opt + n0, lnl + n0, d1 ? d1 + n0 : nullptr, d2 ? d2 + n0 : nullptr,
+                           status ? status + n0 : nullptr, &h->pair_passes);
+    if (rc) return multi ? multi_forward(h, rc) : rc;
+  }
+  return PLK_OK;
+}
+
+int plk_pair_passes(plk_handle h, int64_t* passes) {
+  if (!h || !passes) return fail(h, PLK_ERR_ARG, "null argument");
+  *passes = h->pair_passes;
   return PLK_OK;
 }
 

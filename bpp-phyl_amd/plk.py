@@ -41,7 +41,8 @@ EXPORTS = [
     "plk_root_underflow", "plk_exchange_stride", "plk_exchange_pack", "plk_exchange_reduce",
     "plk_exchange_rank_sums", "plk_clock_records", "plk_clock_waves", "plk_clock_wave_tails",
     "plk_node_posteriors", "plk_set_count_types", "plk_update_count_matrices", "plk_set_count_matrix",
-    "plk_get_count_matrix", "plk_branch_counts", "plk_nni_scores", "plk_nni_passes",
+    "plk_get_count_matrix", "plk_branch_counts", "plk_nni_scores", "plk_nni_passes", "plk_pair_counts",
+    "plk_pair_distances", "plk_pair_passes",
 ]
 
 
@@ -139,6 +140,10 @@ def load(path: str = LIB_PATH) -> ct.CDLL:
         "plk_nni_scores": ([ct.c_void_p, ct.c_int, ip, ip, ip, dp, ct.c_double, ct.c_double, ct.c_double, ct.c_int,
                             dp, dp, dp, dp, ip], ct.c_int),
         "plk_nni_passes": ([ct.c_void_p, P(ct.c_int64)], ct.c_int),
+        "plk_pair_counts": ([ct.c_void_p, ct.c_int, ip, ip, dp], ct.c_int),
+        "plk_pair_distances": ([ct.c_void_p, ct.c_int, ip, ip, ct.c_int, dp, ct.c_double, ct.c_double, ct.c_double,
+                                ct.c_int, dp, dp, dp, dp, ip], ct.c_int),
+        "plk_pair_passes": ([ct.c_void_p, P(ct.c_int64)], ct.c_int),
         "plk_kernel_path": ([ct.c_void_p], ct.c_char_p),
         "plk_compressed_work": ([ct.c_void_p, P(ct.c_int64)], ct.c_int),
         "plk_evaluate": ([ct.c_void_p, ct.c_int, ip, ip, dp, P(plk_op), ct.c_int, ct.c_int, dp, dp], ct.c_int),
@@ -292,6 +297,7 @@ class Engine:
 
     def set_code_table(self, table: np.ndarray):
         t = np.ascontiguousarray(table, dtype=np.float64)
+        self.n_codes = t.shape[0]
         self._chk(self.lib.plk_set_code_table(self.h, t.shape[0], _d(t)))
 
     def set_tip_codes(self, tip: int, codes: np.ndarray):
@@ -564,6 +570,49 @@ class Engine:
             _d(out["t_opt"]), _d(out["delta"]), _d(out["d1"]), _d(out["d2"]), out["status"].ctypes.data_as(ip)))
         passes = ct.c_int64(0)
         self._chk(self.lib.plk_nni_passes(self.h, ct.byref(passes)))
+        out["passes"] = passes.value
+        return out
+
+    def _pairs(self, tip_a, tip_b):
+        a = np.ascontiguousarray(tip_a, dtype=np.int32).ravel()
+        b = np.ascontiguousarray(tip_b, dtype=np.int32).ravel()
+        if len(a) != len(b):
+            raise ValueError("tip_a and tip_b must have one entry per pair")
+        return a, b
+
+    def pair_counts(self, tip_a, tip_b) -> np.ndarray:
+        """plk_pair_counts: [pair, code, code], the summed weight of the patterns at which tip_a
+        shows the first code and tip_b the second (the code table's numbering)."""
+        a, b = self._pairs(tip_a, tip_b)
+        U = getattr(self, "n_codes", 0)
+        out = np.empty((len(a), U, U))
+        ip = ct.POINTER(ct.c_int32)
+        self._chk(self.lib.plk_pair_counts(self.h, len(a), a.ctypes.data_as(ip), b.ctypes.data_as(ip), _d(out)))
+        return out
+
+    def pair_distances(self, tip_a, tip_b, t0=None, t_min: float = 1e-6, t_max: float = 100.0, tol: float = 1e-8,
+                       max_iter: int = 0, model: int = 0) -> dict:
+        """plk_pair_distances for the pairs (tip_a, tip_b): a dict with "t_opt" (the maximum-likelihood
+        distance), "lnl" (the two-sequence log-likelihood there), "d1", "d2" (its derivatives in t),
+        "status" (0 converged, 1 budget spent) per pair, and "passes", the evaluation passes of the
+        slowest pair.  t0 = None starts every pair from its share of differing resolved characters;
+        max_iter = 0 evaluates at the start only."""
+        a, b = self._pairs(tip_a, tip_b)
+        n = len(a)
+        tp = None
+        if t0 is not None:
+            t = np.ascontiguousarray(t0, dtype=np.float64).ravel()
+            if len(t) != n:
+                raise ValueError("t0 must have one entry per pair")
+            tp = _d(t)
+        ip = ct.POINTER(ct.c_int32)
+        out = {k: np.empty(n) for k in ("t_opt", "lnl", "d1", "d2")}
+        out["status"] = np.empty(n, dtype=np.int32)
+        self._chk(self.lib.plk_pair_distances(
+            self.h, n, a.ctypes.data_as(ip), b.ctypes.data_as(ip), model, tp, t_min, t_max, tol, max_iter,
+            _d(out["t_opt"]), _d(out["lnl"]), _d(out["d1"]), _d(out["d2"]), out["status"].ctypes.data_as(ip)))
+        passes = ct.c_int64(0)
+        self._chk(self.lib.plk_pair_passes(self.h, ct.byref(passes)))
         out["passes"] = passes.value
         return out
 

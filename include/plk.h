@@ -469,6 +469,75 @@ int plk_nni_scores(plk_handle h, int n_moves, const int32_t* son, const int32_t*
  * included). */
 int plk_nni_passes(plk_handle h, int64_t* passes);
 
+/* Pairwise sufficient statistics: for every listed pair of tips the table
+ *   N[pair][a][b] = sum_p w_p [code of tip_a at p = a][code of tip_b at p = b],
+ * ordered (a is the code at tip_a; the table of (b, a) is the transpose), n_codes x n_codes in the
+ * numbering of plk_set_code_table, zero rows and columns for codes no tip uses.  The likelihood
+ * of two sequences joined by one branch depends on a pattern through its two codes only, so the
+ * table is all plk_pair_distances reads.  It is formed on the device over the codes in use
+ * (4096-pattern blocks into LDS bins, the blocks added in block order); padding patterns add
+ * nothing.
+ * Exactness: when every weight is an integer and the weights sum to less than 2^53, every
+ * partial sum is exact, so the table equals an integer histogram and is bitwise independent of
+ * summation order, chunking and sharding.  For other weights the sums agree to rounding only,
+ * and the order in which the patterns of one block reach a bin is not fixed.
+ * At most 90 codes may be in use over the uploaded tips (PLK_ERR_UNSUPPORTED beyond: the bins of
+ * a workgroup are 8 U^2 bytes of LDS); the code table itself may be longer.
+ * PLK_ERR_ARG: tip_a == tip_b, an index outside [0, n_tips), n_pairs <= 0, a null pointer.
+ * PLK_ERR_STATE: before plk_set_code_table or the codes of a named tip.  PLK_ERR_UNSUPPORTED
+ * under a communicator.  Needs no traversal, partial, P(t) or flag and changes none, nor
+ * plk_kernel_path or the next plk_root_loglik.  Device staging is bounded (256 MiB; PLK_TUNE
+ * PAIR_CAP_KB lowers it): longer pair lists run chunk by chunk.  On a multi-device handle every
+ * shard counts its own patterns and the parent adds the tables in shard order. */
+int plk_pair_counts(plk_handle h, int n_pairs, const int32_t* tip_a, const int32_t* tip_b,
+                    double* counts /* n_pairs x n_codes x n_codes, caller's code numbering */);
+
+/* Maximum-likelihood distance of every listed pair: the branch length t that maximises the
+ * likelihood of the two sequences under `model` (its real eigen system V, Vinv, lambda), the
+ * rate classes and pi.  With init the code table,
+ *   alpha[a][k] = sum_x pi_x init[a][x] V[x][k],   beta[k][b] = sum_y Vinv[k][y] init[b][y],
+ *   delta[a][b] = sum_x pi_x init[a][x] init[b][x],
+ *   l_ab(t) = sum_c p_c sum_k alpha[a][k] beta[k][b] exp(lambda_k r_c t),
+ *   F(t) = sum_ab N_ab log l_ab,  d1 = sum N l'/l,  d2 = sum N (l''/l - (l'/l)^2)
+ * over the entries with N > 0 of the pair's table (plk_pair_counts), formed on the device and
+ * never brought to the host.  While t max|lambda_k r_c| <= 1, l_ab is summed as
+ * delta_ab + sum alpha beta expm1(lambda r t): for a != b it is O(t), summed from O(1) terms
+ * (plk_nni_scores has the same switch).  An entry whose l is not a positive finite number adds 0
+ * to all sums.
+ * max_iter == 0: every pair is evaluated at its start (t_opt = t0; status 0).  max_iter > 0: the
+ * ascent of plk_nni_scores, one workgroup per pair, wholly on the device -- from a point
+ * (t, F, d1, d2) the proposal is t' = t - d1 / d2 when d2 < 0, else 2 t when d1 > 0, else t / 2,
+ * clamped to [t_min, t_max]; after a rejected trial it is the midpoint of t and that trial.  A
+ * pair is converged when |t' - t| <= tol max(t, t_min); otherwise t' is evaluated, at most
+ * max_iter times after the first evaluation, and accepted when F(t') >= F(t), decided on
+ * F(t') - F(t) = sum N log1p((l(t') - l(t)) / l(t)) with l(t') - l(t) from
+ * expm1(lambda r (t' - t)).  t_opt, d1, d2 are those of the last accepted point, lnl is F there
+ * (F(t0) plus the accepted changes): the two-sequence log-likelihood.  status: 0 converged,
+ * 1 budget spent.  All sums run in a fixed order, so a pair's result does not depend on its
+ * place in the list, on chunking or (integer weights) on sharding.
+ * t0 == NULL: the start comes from the table on the device.  A code is resolved when its
+ * code-table row has exactly one non-zero entry; g is the weight of the entries with both codes
+ * resolved, d the weight of those whose states differ; t0 = d / g clamped to [t_min, t_max], or
+ * t_min when g = 0.
+ * Replaces DistanceEstimation::computeMatrix (Distance/DistanceEstimation.cpp:647-687) and its
+ * TwoTreeLikelihood (:474-521).  Deviations: Newton to `tol` in the place of the reference's
+ * optimiser; the d / g start of the reference (:671-673) compares raw characters, so an
+ * ambiguity code against a state counts as a difference there and is left out here (a start
+ * only); real eigen systems only.
+ * PLK_ERR_ARG as plk_pair_counts, and for t_min <= 0, t_max < t_min, tol < 0, max_iter < 0, a
+ * model out of range or a t0 outside the bounds.  PLK_ERR_STATE as plk_pair_counts, and before
+ * the rates and pi are set or when `model` has no eigen system (only plk_set_pmatrix).
+ * PLK_ERR_UNSUPPORTED as plk_pair_counts.  A multi-device handle sums the shards' tables on the
+ * host and runs the ascent on its first shard.  With plk_set_timing the count launches are timed
+ * as PLK_TIME_TABLES and the Newton launches as PLK_TIME_ROOT. */
+int plk_pair_distances(plk_handle h, int n_pairs, const int32_t* tip_a, const int32_t* tip_b,
+                       int model, const double* t0 /* n_pairs, or NULL */,
+                       double t_min, double t_max, double tol, int max_iter,
+                       double* t_opt, double* lnl, double* d1, double* d2 /* each n_pairs; d1, d2 nullable */,
+                       int32_t* status /* n_pairs, nullable */);
+/* Evaluation passes of the slowest pair of the last plk_pair_distances on this handle. */
+int plk_pair_passes(plk_handle h, int64_t* passes);
+
 /* Instrumentation: HIP-event timing on the handle's stream of the kernels selected
  * by the mask given to plk_set_timing (0 = off).  Each timed launch adds an event
  * pair to the stream, so time only what is needed. */
