@@ -16,6 +16,7 @@
 #include "plk_post.hpp"
 #include "plk_map.hpp"
 #include "plk_nni.hpp"
+#include "plk_rell.hpp"
 #include "plk_pair.hpp"
 #include "plk_exchange.hpp"
 
@@ -426,6 +427,16 @@ struct plk_handle_s {
   char* d_pair = nullptr;
   size_t d_pair_cap = 0;
   int64_t pair_passes = 0;              // evaluation passes of the slowest pair, last plk_pair_distances
+  // RELL resampling (plk_rell.hpp): site rows [rell_n_rows][n_pad] and replicate weights
+  // [rell_R][n_pad], padding 0.0; a multi-device parent keeps the two counts only
+  double* rell_rows = nullptr;
+  int rell_n_rows = 0;
+  double* rell_W = nullptr;
+  int rell_R = 0;
+  char* rell_stage = nullptr;           // a chunk's block partials, its chain results and seeds
+  size_t rell_stage_cap = 0;
+  int32_t* rell_bad = nullptr;          // non-finite values per workgroup (plk_site_row_from_root)
+  int64_t rell_passes = 0;              // block-partial launches of the last plk_replicate_sums
   // multi-device handle (plk_create_multi): one shard handle per device over contiguous,
   // block-aligned pattern ranges; the parent owns no device memory
   std::vector<plk_handle> shards;
@@ -1227,7 +1238,8 @@ int plk_destroy(plk_handle h) {
                   h->d2_sums, h->d_dprog, h->pmatsT, h->d_ucodes, h->d_units, h->d_cherry3,
                   h->d_cherry_tips, h->d_cherry, h->d_drb, h->d_drm, h->dr_blk, h->dr_out, h->d_drpre, h->d_sbctr,
                   h->d_cherry_rows, h->d_kidsl, h->d_cls, h->d_ucodes_dc, h->d_units_start, h->d_post, h->post_buf,
-                  h->count_G, h->wmats, h->d_mapb, h->map_blk, h->d_mapreq, h->d_nni, h->nni_vit, h->d_pair};
+                  h->count_G, h->wmats, h->d_mapb, h->map_blk, h->d_mapreq, h->d_nni, h->nni_vit, h->d_pair,
+                  h->rell_rows, h->rell_W, h->rell_stage, h->rell_bad};
   for (void* p : bufs)
     if (p) hipFree(p);
   if (h->h_req) (void)hipHostFree(h->h_req);
@@ -4507,6 +4519,43 @@ int nni_eval_local(plk_handle h, int chunk, int n_act, const int32_t* idx, const
     std::copy(hbuf + (size_t)r * nB, hbuf + (size_t)(r + 1) * nB, blocks + (size_t)r * nB_total + B0);
   return PLK_OK;
 }
+
+// Stage 2 of plk_nni_site_rows: log rho of the built chunk's moves 0 .. cn at the lengths t[]
+// into the site rows from `row0` on (nni_rows_kernel), nothing reduced.
+int nni_rows_local(plk_handle h, int chunk, int cn, const int32_t* model, const double* t, int row0) {
+  const int S = h->S, C = h->C, CS = C * S;
+  hipSetDevice(h->device);
+  const NniStage st(chunk, CS);
+  const size_t off_idx = (size_t)cn * 2 * sizeof(double), off_model = off_idx + (size_t)cn * sizeof(int32_t);
+  double* ht = reinterpret_cast<double*>(h->h_nni);
+  int32_t* hi = reinterpret_cast<int32_t*>(h->h_nni + off_idx);
+  for (int i = 0; i < cn; ++i) ht[i] = ht[cn + i] = t[i], hi[i] = i, hi[cn + i] = model[i];
+  HIPCHK(h, hipMemcpyAsync(h->d_nni + st.req, h->h_nni, NniStage::req_bytes(cn), hipMemcpyHostToDevice, h->stream));
+  NniEvalArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.coef = (const double*)h->post_buf;
+  a.weights = h->weights;
+  a.idx = reinterpret_cast<const int32_t*>(h->d_nni + st.req + off_idx);
+  a.model = reinterpret_cast<const int32_t*>(h->d_nni + st.req + off_model);
+  a.t = reinterpret_cast<const double*>(h->d_nni + st.req);
+  a.rates = h->rates;
+  a.lambda = h->lambda;
+  a.ex = reinterpret_cast<double*>(h->d_nni + st.ex);
+  a.n_pad = h->n_pad;
+  a.n_patterns = h->n_patterns;
+  a.S = S;
+  a.C = C;
+  a.n_blk = (int)(h->n_pad / kNniThreads);
+  a.n_act = cn;
+  nni_expo_kernel<<<(unsigned)((cn * CS + 63) / 64), 64, 0, h->stream>>>(a);
+  HIPCHK(h, hipGetLastError());
+  TimedSpan span(h, PLK_TIME_ROOT, 2);
+  nni_rows_kernel<<<dim3((unsigned)a.n_blk, (unsigned)cn), kNniThreads, 0, h->stream>>>(a, h->rell_rows + (size_t)row0 * h->n_pad);
+  HIPCHK(h, hipGetLastError());
+  span.stop();
+  HIPCHK(h, hipStreamSynchronize(h->stream));  // the pinned request is free again
+  return PLK_OK;
+}
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -4844,14 +4893,15 @@ int launch_block_sums(plk_handle h) {
 // 4096-pattern block sums, the RCCL exchange under a communicator, and the per-pattern lnL
 // copy; root_finish waits and sums.  Split so that a multi-device handle can have every
 // device's reduction in flight before it waits for the first.
-int root_launch(plk_handle h, int root, double* site_lnl) {
+int root_launch(plk_handle h, int root, double* site_lnl, bool site_dev = false) {
+  const bool want_site = site_lnl || site_dev;  // site_dev: the per-pattern lnL stays in h->site_lnl
   if (root < h->n_tips || root >= h->n_nodes) return fail(h, PLK_ERR_ARG, "bad root node %d", root);
   if (!h->pi_set || !h->rates_set) return fail(h, PLK_ERR_STATE, "root frequencies / category rates not set");
   hipSetDevice(h->device);
   if (h->fused_lnl_valid && h->fused_lnl_root == root) {
     // the fused traversal already reduced the root: only the block sums remain (with one class
     // per workgroup they are formed too -- again if the communicator changed where they go)
-    if (h->fused_cls_blocks && h->fused_cls_blocks == block_target(h) && (h->cls_site_written || !site_lnl)) {
+    if (h->fused_cls_blocks && h->fused_cls_blocks == block_target(h) && (h->cls_site_written || !want_site)) {
       if (h->comm) {
         flag_slot_kernel<<<1, 1, 0, h->stream>>>(h->d_uflow, h->d_blk_local + h->comm_stride - 1);
         HIPCHK(h, hipGetLastError());
@@ -4860,7 +4910,7 @@ int root_launch(plk_handle h, int root, double* site_lnl) {
       // again: block sums to the communicator's buffer, or the per-pattern lnL asked for
       h->fused_cls_blocks = block_target(h);
       if (int rc = launch_cls_blocks(h, (h->flags & PLK_FLAG_NONNEG_GUARD) ? 1 : 0,
-                                     (h->flags & PLK_FLAG_SCALING) ? nullptr : h->d_uflow, site_lnl != nullptr))
+                                     (h->flags & PLK_FLAG_SCALING) ? nullptr : h->d_uflow, want_site))
         return rc;
       HIPCHK(h, hipGetLastError());
       if (h->comm) {
@@ -4983,6 +5033,140 @@ int comm_sum_values(plk_handle h, double* v, size_t n) {
   HIPCHK(h, hipMemcpyAsync(all.data(), h->d_xch_all, all.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   xchg::rank_sums(all.data(), (int)R, n, v);
+  return PLK_OK;
+}
+
+// ---------------------------------------------------------------------------
+// RELL resampling (plk_rell.hpp): local stages; the extern "C" calls fan them out over shards.
+// ---------------------------------------------------------------------------
+constexpr size_t kRellStageCap = (size_t)2 << 30;  // block partials of one chunk of replicates x rows
+
+int rell_free(plk_handle h, double** p) {
+  if (!*p) return PLK_OK;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, hipFree(*p));
+  *p = nullptr;
+  return PLK_OK;
+}
+
+int rell_reserve_local(plk_handle h, int n_rows) {
+  hipSetDevice(h->device);
+  h->rell_n_rows = 0;
+  if (int rc = rell_free(h, &h->rell_rows)) return rc;
+  if (n_rows == 0) return PLK_OK;
+  const size_t bytes = (size_t)n_rows * h->n_pad * sizeof(double);
+  if (int rc = dalloc(h, (void**)&h->rell_rows, bytes)) return rc;
+  HIPCHK(h, hipMemsetAsync(h->rell_rows, 0, bytes, h->stream));
+  h->rell_n_rows = n_rows;
+  return PLK_OK;
+}
+
+// W: the first value of this handle's patterns in replicate 0, replicates `ld` doubles apart
+int rell_weights_local(plk_handle h, int R, const double* W, int64_t ld) {
+  hipSetDevice(h->device);
+  h->rell_R = 0;
+  if (int rc = rell_free(h, &h->rell_W)) return rc;
+  if (R == 0) return PLK_OK;
+  const size_t pitch = (size_t)h->n_pad * sizeof(double);
+  if (int rc = dalloc(h, (void**)&h->rell_W, (size_t)R * pitch)) return rc;
+  HIPCHK(h, hipMemsetAsync(h->rell_W, 0, (size_t)R * pitch, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, hipMemcpy2D(h->rell_W, pitch, W, (size_t)ld * sizeof(double), (size_t)h->n_patterns * sizeof(double),
+                        (size_t)R, hipMemcpyHostToDevice));
+  h->rell_R = R;
+  return PLK_OK;
+}
+
+int rell_row_check(plk_handle h, int first, int n) {
+  if (first < 0 || n < 1 || first > h->rell_n_rows - n)
+    return fail(h, PLK_ERR_ARG, "site rows [%d, %d + %d) outside the %d reserved", first, first, n, h->rell_n_rows);
+  return PLK_OK;
+}
+
+// The root reduction exactly as plk_root_loglik(site_lnl != NULL) runs it, its per-pattern values
+// kept in h->site_lnl and copied to the row on the device.  The underflow flag is put back: the
+// reduction of another root than the last one's must not be seen by plk_root_underflow.
+int rell_from_root_local(plk_handle h, int root, int row, int64_t* n_bad) {
+  if (h->comm) return fail(h, PLK_ERR_UNSUPPORTED, "site rows under a communicator");
+  if (int rc = rell_row_check(h, row, 1)) return rc;
+  hipSetDevice(h->device);
+  const int n_wg = (int)(h->n_pad / 256);
+  if (!h->rell_bad)
+    if (int rc = dalloc(h, (void**)&h->rell_bad, (size_t)n_wg * sizeof(int32_t))) return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  const int32_t flag = *(volatile int32_t*)h->h_uflow;
+  if (int rc = root_launch(h, root, nullptr, true)) return rc;
+  rell_row_from_site_kernel<<<(unsigned)n_wg, 256, 0, h->stream>>>(h->site_lnl, h->rell_rows + (size_t)row * h->n_pad,
+                                                                  h->rell_bad, h->n_patterns);
+  HIPCHK(h, hipGetLastError());
+  std::vector<int32_t> bad((size_t)n_wg);
+  HIPCHK(h, hipMemcpyAsync(bad.data(), h->rell_bad, bad.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  *(volatile int32_t*)h->h_uflow = flag;
+  int64_t n = 0;
+  for (int32_t b : bad) n += b;
+  *n_bad = n;
+  return PLK_OK;
+}
+
+// carve-up of rell_stage for a chunk of E = Rc x Mc elements over nB blocks
+struct RellStage {
+  size_t part, part_abs, out, seed, bytes;  // out / seed: E values, then E of the absolute sums
+  RellStage(int64_t nB, size_t E, bool abs) {
+    const size_t k = abs ? 2 : 1;
+    part = 0;
+    part_abs = (size_t)nB * E * sizeof(double);
+    out = k * (size_t)nB * E * sizeof(double);
+    seed = out + k * E * sizeof(double);
+    bytes = seed + k * E * sizeof(double);
+  }
+};
+
+// Step 1 of the summation rule for the chunk (r0, Rc) x (m0, Mc): this handle's block partials
+int rell_partials_local(plk_handle h, int r0, int Rc, int m0, int Mc, bool abs) {
+  hipSetDevice(h->device);
+  const RellStage st(h->n_blocks, (size_t)Rc * Mc, abs);
+  if (int rc = ensure_cap(h, (void**)&h->rell_stage, &h->rell_stage_cap, st.bytes)) return rc;
+  RellArgs a;
+  a.W = h->rell_W + (size_t)r0 * h->n_pad;
+  a.rows = h->rell_rows + (size_t)m0 * h->n_pad;
+  a.part = reinterpret_cast<double*>(h->rell_stage + st.part);
+  a.part_abs = reinterpret_cast<double*>(h->rell_stage + st.part_abs);
+  a.n_pad = h->n_pad;
+  a.Rc = Rc;
+  a.Mc = Mc;
+  const dim3 grid((unsigned)((Mc + kRellTile - 1) / kRellTile), (unsigned)((Rc + kRellTile - 1) / kRellTile), (unsigned)h->n_blocks);
+  TimedSpan span(h, PLK_TIME_ROOT, 2);
+  if (abs)
+    rell_partial_kernel<true><<<grid, kRellThreads, 0, h->stream>>>(a);
+  else
+    rell_partial_kernel<false><<<grid, kRellThreads, 0, h->stream>>>(a);
+  HIPCHK(h, hipGetLastError());
+  span.stop();
+  return PLK_OK;
+}
+
+// Step 2: this handle's blocks continue the chains of g (and gabs) -- seeded with them unless
+// `first` -- and the results come back in their place.
+int rell_chain_local(plk_handle h, int Rc, int Mc, bool abs, bool first, double* g, double* gabs) {
+  hipSetDevice(h->device);
+  const size_t E = (size_t)Rc * Mc, k = abs ? 2 : 1;
+  const RellStage st(h->n_blocks, E, abs);
+  double* out = reinterpret_cast<double*>(h->rell_stage + st.out);
+  double* seed = reinterpret_cast<double*>(h->rell_stage + st.seed);
+  if (!first) {
+    HIPCHK(h, hipMemcpyAsync(seed, g, E * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (abs) HIPCHK(h, hipMemcpyAsync(seed + E, gabs, E * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  }
+  for (size_t i = 0; i < k; ++i) {
+    const double* part = reinterpret_cast<const double*>(h->rell_stage + (i ? st.part_abs : st.part));
+    rell_chain_kernel<<<(unsigned)((E + 255) / 256), 256, 0, h->stream>>>(part, first ? nullptr : seed + i * E, out + i * E,
+                                                                        (int64_t)E, h->n_blocks);
+    HIPCHK(h, hipGetLastError());
+  }
+  HIPCHK(h, hipMemcpyAsync(g, out, E * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (abs) HIPCHK(h, hipMemcpyAsync(gabs, out + E, E * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
   return PLK_OK;
 }
 
@@ -5690,6 +5874,148 @@ int plk_nni_scores(plk_handle h, int n_moves, const int32_t* son, const int32_t*
 int plk_nni_passes(plk_handle h, int64_t* passes) {
   if (!h || !passes) return fail(h, PLK_ERR_ARG, "null argument");
   *passes = h->nni_passes;
+  return PLK_OK;
+}
+
+int plk_site_rows_reserve(plk_handle h, int n_rows) {
+  env_refresh();
+  if (!h || n_rows < 0) return fail(h, PLK_ERR_ARG, "bad row count %d", n_rows);
+  if (h->shards.empty()) return rell_reserve_local(h, n_rows);
+  h->rell_n_rows = 0;
+  if (int rc = multi_each(h, [&](plk_handle x) { return rell_reserve_local(x, n_rows); })) return rc;
+  h->rell_n_rows = n_rows;
+  return PLK_OK;
+}
+
+int plk_site_row_set(plk_handle h, int row, const double* v) {
+  env_refresh();
+  if (!h || !v) return fail(h, PLK_ERR_ARG, "null argument");
+  if (int rc = rell_row_check(h, row, 1)) return rc;
+  if (!h->shards.empty()) return multi_slices(h, [&](plk_handle x, int64_t a) { return plk_site_row_set(x, row, v + a); });
+  hipSetDevice(h->device);
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, hipMemcpy(h->rell_rows + (size_t)row * h->n_pad, v, (size_t)h->n_patterns * sizeof(double), hipMemcpyHostToDevice));
+  return PLK_OK;
+}
+
+int plk_site_row_get(plk_handle h, int row, double* v) {
+  env_refresh();
+  if (!h || !v) return fail(h, PLK_ERR_ARG, "null argument");
+  if (int rc = rell_row_check(h, row, 1)) return rc;
+  if (!h->shards.empty()) return multi_slices(h, [&](plk_handle x, int64_t a) { return plk_site_row_get(x, row, v + a); });
+  hipSetDevice(h->device);
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, hipMemcpy(v, h->rell_rows + (size_t)row * h->n_pad, (size_t)h->n_patterns * sizeof(double), hipMemcpyDeviceToHost));
+  return PLK_OK;
+}
+
+int plk_site_row_from_root(plk_handle h, int root, int row, int64_t* n_bad) {
+  env_refresh();
+  if (!h) return fail(h, PLK_ERR_ARG, "null handle");
+  if (int rc = rell_row_check(h, row, 1)) return rc;
+  int64_t n = 0;
+  if (h->shards.empty()) {
+    if (int rc = rell_from_root_local(h, root, row, &n)) return rc;
+  } else {
+    std::vector<int64_t> bad(h->shards.size(), 0);
+    if (int rc = multi_run(h, [&](size_t i) { return rell_from_root_local(h->shards[i], root, row, &bad[i]); })) return rc;
+    for (int64_t b : bad) n += b;
+  }
+  if (n_bad) *n_bad = n;
+  return PLK_OK;
+}
+
+int plk_nni_site_rows(plk_handle h, int n_moves, const int32_t* son, const int32_t* uncle, const int32_t* model,
+                      const double* t, int first_row) {
+  env_refresh();
+  if (!h) return fail(h, PLK_ERR_ARG, "null handle");
+  if (n_moves <= 0 || !son || !uncle) return fail(h, PLK_ERR_ARG, "bad move list (%d moves)", n_moves);
+  if (!t) return fail(h, PLK_ERR_ARG, "t is required");
+  for (int i = 0; i < n_moves; ++i)
+    if (!(t[i] > 0.0 && t[i] <= 1.79769313486231570815e308))
+      return fail(h, PLK_ERR_ARG, "move %d: t = %g is not a positive finite length", i, t[i]);
+  const bool multi = !h->shards.empty();
+  plk_handle x0 = multi ? h->shards[0] : h;
+  std::vector<NniMove> recs;
+  int rc = nni_plan(x0, n_moves, son, uncle, model, recs);
+  if (rc) return multi ? multi_forward(h, rc) : rc;
+  if ((rc = rell_row_check(h, first_row, n_moves))) return rc;
+  auto each = [&](const std::function<int(plk_handle, int64_t)>& f) { return multi ? multi_slices(h, f) : f(h, 0); };
+  const int CS = x0->C * x0->S;
+  int64_t n_pad = x0->n_pad;
+  for (plk_handle s : h->shards) n_pad = std::max(n_pad, s->n_pad);
+  // coefficient staging as plk_nni_scores: chunks of moves under kNniStageCap (PLK_TUNE NNI_CAP_KB)
+  const size_t cap = (size_t)tune_int("NNI_CAP_KB", (int)(kNniStageCap >> 10), 1, (int)(kNniStageCap >> 10)) << 10;
+  const size_t per_move = (size_t)(CS + kNniExtra) * n_pad * sizeof(double);
+  const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_moves, cap / per_move));
+  std::vector<int32_t> mdl((size_t)n_moves);
+  for (int i = 0; i < n_moves; ++i) mdl[(size_t)i] = recs[(size_t)i].model;
+  for (int n0 = 0; n0 < n_moves; n0 += chunk) {
+    const int cn = std::min(chunk, n_moves - n0);
+    if ((rc = each([&](plk_handle x, int64_t) { return nni_build_local(x, recs.data() + n0, cn, chunk, n0 == 0); }))) return rc;
+    if ((rc = each([&](plk_handle x, int64_t) { return nni_rows_local(x, chunk, cn, mdl.data() + n0, t + n0, first_row + n0); })))
+      return rc;
+  }
+  return PLK_OK;
+}
+
+int plk_set_replicate_weights(plk_handle h, int R, const double* W) {
+  env_refresh();
+  if (!h || R < 0 || (R > 0 && !W)) return fail(h, PLK_ERR_ARG, "bad replicate weights (%d replicates)", R);
+  if (h->shards.empty()) return rell_weights_local(h, R, W, h->n_patterns);
+  h->rell_R = 0;
+  if (int rc = multi_slices(h, [&](plk_handle x, int64_t a) { return rell_weights_local(x, R, W ? W + a : nullptr, h->n_patterns); }))
+    return rc;
+  h->rell_R = R;
+  return PLK_OK;
+}
+
+int plk_replicate_sums(plk_handle h, int first_row, int n_rows, double* G, double* Gabs) {
+  env_refresh();
+  if (!h || !G) return fail(h, PLK_ERR_ARG, "null argument");
+  if (h->comm) return fail(h, PLK_ERR_UNSUPPORTED, "replicate sums under a communicator");
+  if (h->rell_R == 0 || h->rell_n_rows == 0)
+    return fail(h, PLK_ERR_STATE, "no replicate weights (plk_set_replicate_weights) or no site rows (plk_site_rows_reserve)");
+  if (int rc = rell_row_check(h, first_row, n_rows)) return rc;
+  const bool multi = !h->shards.empty(), abs = Gabs != nullptr;
+  const int R = h->rell_R;
+  int64_t nB = h->n_blocks;  // the most blocks of any shard bound the staging
+  if (multi) {
+    nB = 0;
+    for (plk_handle s : h->shards) nB = std::max<int64_t>(nB, s->n_blocks);
+  }
+  if (nB > 65535) return fail(h, PLK_ERR_UNSUPPORTED, "%lld pattern blocks on one device (at most 65535)", (long long)nB);
+  // chunks of replicates x rows whose block partials stay under kRellStageCap (PLK_TUNE RELL_CAP_KB)
+  const size_t cap = (size_t)tune_int("RELL_CAP_KB", (int)(kRellStageCap >> 10), 1, (int)(kRellStageCap >> 10)) << 10;
+  const size_t elems = std::max<size_t>(1, cap / ((size_t)nB * sizeof(double) * (abs ? 2 : 1)));
+  const int Rc = (int)std::min<size_t>((size_t)R, elems);
+  const int Mc = (int)std::min<size_t>((size_t)n_rows, std::max<size_t>(1, elems / (size_t)Rc));
+  std::vector<double> g((size_t)Rc * Mc), ga(abs ? g.size() : 0);
+  h->rell_passes = 0;
+  for (int r0 = 0; r0 < R; r0 += Rc)
+    for (int m0 = 0; m0 < n_rows; m0 += Mc) {
+      const int rc_n = std::min(Rc, R - r0), mc_n = std::min(Mc, n_rows - m0);
+      if (multi) {
+        // the partials of all shards side by side, then the cheap chains shard after shard
+        if (int rc = multi_each(h, [&](plk_handle x) { return rell_partials_local(x, r0, rc_n, first_row + m0, mc_n, abs); })) return rc;
+        for (size_t i = 0; i < h->shards.size(); ++i)
+          if (int rc = rell_chain_local(h->shards[i], rc_n, mc_n, abs, i == 0, g.data(), ga.data())) return multi_forward(h, rc);
+      } else {
+        if (int rc = rell_partials_local(h, r0, rc_n, first_row + m0, mc_n, abs)) return rc;
+        if (int rc = rell_chain_local(h, rc_n, mc_n, abs, true, g.data(), ga.data())) return rc;
+      }
+      h->rell_passes++;
+      for (int r = 0; r < rc_n; ++r) {
+        std::copy(g.begin() + (size_t)r * mc_n, g.begin() + (size_t)(r + 1) * mc_n, G + (size_t)(r0 + r) * n_rows + m0);
+        if (abs) std::copy(ga.begin() + (size_t)r * mc_n, ga.begin() + (size_t)(r + 1) * mc_n, Gabs + (size_t)(r0 + r) * n_rows + m0);
+      }
+    }
+  return PLK_OK;
+}
+
+int plk_replicate_passes(plk_handle h, int64_t* launches) {
+  if (!h || !launches) return fail(h, PLK_ERR_ARG, "null argument");
+  *launches = h->rell_passes;
   return PLK_OK;
 }
 

@@ -52,6 +52,33 @@ class NNIHomogeneousTreeLikelihood : public DRHomogeneousTreeLikelihood, public 
   void topologyChangeSuccessful(const TopologyChangeEvent&) override { scoresValid_ = false; }
   void topologyChangePerformed(const TopologyChangeEvent&) override { scoresValid_ = false; }
   size_t getNumberOfScoreCalls() const { return scoreCalls_; }
+
+  // Local bootstrap proportions (RELL over the three NNI configurations around a branch, the
+  // "LBP" of MOLPHY), keyed by the id of the lower node of every internal branch p whose father
+  // g and itself have at most three sons.  The rivals of p are the interchanges (s, uncle) for
+  // every son s of p, each at the length testNNI re-estimated (the cached plk_nni_scores
+  // answers).  One plk_nni_site_rows call writes log rho per pattern of every rival, the
+  // weights are bootstrap(nSites) counts per replicate mapped to patterns, and one
+  // plk_replicate_sums call returns the resampled differences to the current tree, whose own is
+  // 0.  Changes no parameter, no cached score and no later getValue().  The rows and weights stay
+  // on the engine until the next call or plk_site_rows_reserve(engine, 0): plk_replicate_sums
+  // over rows 0 .. (the sum of getLocalBootstrapRivals()) returns the same sums again.
+  std::map<int, double> computeLocalBootstrap(size_t nReplicates) const;
+  // frees those rows and weights (replicates x patterns doubles and one row per rival)
+  void releaseLocalBootstrap() const;
+  // the branches of the last computeLocalBootstrap in row order and the rivals of each
+  const std::vector<int>& getLocalBootstrapNodeIds() const { return lbpIds_; }
+  const std::vector<size_t>& getLocalBootstrapRivals() const { return lbpRivals_; }
+  // The share of replicates in which no rival beats the current configuration: G is
+  // replicates x (sum of rivals), replicate-major, the rivals of a branch side by side.  A
+  // replicate counts 0 when a rival's sum is positive, else 1 / k with k = 1 + the rivals whose
+  // sum is exactly 0 (tied at the top with the current configuration).
+  static std::vector<double> localBootstrapFromSums(const std::vector<double>& G, size_t replicates,
+                                                    const std::vector<size_t>& rivals);
+
+ private:
+  mutable std::vector<int> lbpIds_;
+  mutable std::vector<size_t> lbpRivals_;
 };
 
 }  // namespace bpp

@@ -43,6 +43,15 @@ class TreeLikelihood : public AbstractParametrizable {
   virtual double getLogLikelihoodForASite(size_t site) const = 0;
   virtual double getLikelihoodForASite(size_t site) const = 0;
   virtual size_t getNumberOfSites() const = 0;
+  // every site's log-likelihood: the per-pattern values through the root pattern links
+  // (Likelihood/AbstractTreeLikelihood.cpp getLogLikelihoodForEachSite).  Not virtual: it is
+  // fully determined by getNumberOfSites() and getLogLikelihoodForASite(), which every likelihood
+  // class already overrides, so no class has anything of its own to put here.
+  std::vector<double> getLogLikelihoodForEachSite() const {
+    std::vector<double> l(getNumberOfSites());
+    for (size_t i = 0; i < l.size(); i++) l[i] = getLogLikelihoodForASite(i);
+    return l;
+  }
   virtual size_t getNumberOfStates() const = 0;
   virtual size_t getNumberOfClasses() const = 0;
   virtual const Tree& getTree() const = 0;

@@ -42,7 +42,9 @@ EXPORTS = [
     "plk_exchange_rank_sums", "plk_clock_records", "plk_clock_waves", "plk_clock_wave_tails",
     "plk_node_posteriors", "plk_set_count_types", "plk_update_count_matrices", "plk_set_count_matrix",
     "plk_get_count_matrix", "plk_branch_counts", "plk_nni_scores", "plk_nni_passes", "plk_pair_counts",
-    "plk_pair_distances", "plk_pair_passes",
+    "plk_pair_distances", "plk_pair_passes", "plk_site_rows_reserve", "plk_site_row_set", "plk_site_row_get",
+    "plk_site_row_from_root", "plk_nni_site_rows", "plk_set_replicate_weights", "plk_replicate_sums",
+    "plk_replicate_passes",
 ]
 
 
@@ -144,6 +146,14 @@ def load(path: str = LIB_PATH) -> ct.CDLL:
         "plk_pair_distances": ([ct.c_void_p, ct.c_int, ip, ip, ct.c_int, dp, ct.c_double, ct.c_double, ct.c_double,
                                 ct.c_int, dp, dp, dp, dp, ip], ct.c_int),
         "plk_pair_passes": ([ct.c_void_p, P(ct.c_int64)], ct.c_int),
+        "plk_site_rows_reserve": ([ct.c_void_p, ct.c_int], ct.c_int),
+        "plk_site_row_set": ([ct.c_void_p, ct.c_int, dp], ct.c_int),
+        "plk_site_row_get": ([ct.c_void_p, ct.c_int, dp], ct.c_int),
+        "plk_site_row_from_root": ([ct.c_void_p, ct.c_int, ct.c_int, P(ct.c_int64)], ct.c_int),
+        "plk_nni_site_rows": ([ct.c_void_p, ct.c_int, ip, ip, ip, dp, ct.c_int], ct.c_int),
+        "plk_set_replicate_weights": ([ct.c_void_p, ct.c_int, dp], ct.c_int),
+        "plk_replicate_sums": ([ct.c_void_p, ct.c_int, ct.c_int, dp, dp], ct.c_int),
+        "plk_replicate_passes": ([ct.c_void_p, P(ct.c_int64)], ct.c_int),
         "plk_kernel_path": ([ct.c_void_p], ct.c_char_p),
         "plk_compressed_work": ([ct.c_void_p, P(ct.c_int64)], ct.c_int),
         "plk_evaluate": ([ct.c_void_p, ct.c_int, ip, ip, dp, P(plk_op), ct.c_int, ct.c_int, dp, dp], ct.c_int),
@@ -615,6 +625,76 @@ class Engine:
         self._chk(self.lib.plk_pair_passes(self.h, ct.byref(passes)))
         out["passes"] = passes.value
         return out
+
+    # RELL resampling: site rows on the device, replicate weights, their product
+
+    def site_rows_reserve(self, n_rows: int):
+        """plk_site_rows_reserve: n_rows device rows of one double per pattern, all 0.0 (rows of an
+        earlier reservation are lost; 0 frees them)."""
+        self._chk(self.lib.plk_site_rows_reserve(self.h, int(n_rows)))
+
+    def site_row_set(self, row: int, v: np.ndarray):
+        v = np.ascontiguousarray(v, dtype=np.float64).ravel()
+        if len(v) != self.P:
+            raise ValueError("a site row has one value per pattern")
+        self._chk(self.lib.plk_site_row_set(self.h, int(row), _d(v)))
+
+    def site_row_get(self, row: int) -> np.ndarray:
+        v = np.empty(self.P)
+        self._chk(self.lib.plk_site_row_get(self.h, int(row), _d(v)))
+        return v
+
+    def site_row_from_root(self, root: int, row: int) -> int:
+        """plk_site_row_from_root: the row receives the per-pattern lnL of root_loglik(want_sites=True)
+        without leaving the device; returns the number of non-finite values stored as 0.0."""
+        n = ct.c_int64(0)
+        self._chk(self.lib.plk_site_row_from_root(self.h, int(root), int(row), ct.byref(n)))
+        return n.value
+
+    def nni_site_rows(self, son, uncle, t, first_row: int, model=None):
+        """plk_nni_site_rows: row first_row + i receives log rho per pattern of the move (son[i],
+        uncle[i]) with branch p at length t[i] -- the swapped tree's site lnL minus the current one's."""
+        s = np.ascontiguousarray(son, dtype=np.int32).ravel()
+        u = np.ascontiguousarray(uncle, dtype=np.int32).ravel()
+        tt = np.ascontiguousarray(t, dtype=np.float64).ravel()
+        n = len(s)
+        if len(u) != n or len(tt) != n:
+            raise ValueError("son, uncle and t must have one entry per move")
+        ip = ct.POINTER(ct.c_int32)
+        mp = None
+        if model is not None:
+            m = np.ascontiguousarray(model, dtype=np.int32).ravel()
+            if len(m) != n:
+                raise ValueError("model must have one entry per move")
+            mp = m.ctypes.data_as(ip)
+        self._chk(self.lib.plk_nni_site_rows(self.h, n, s.ctypes.data_as(ip), u.ctypes.data_as(ip), mp, _d(tt),
+                                             int(first_row)))
+
+    def set_replicate_weights(self, W):
+        """plk_set_replicate_weights: W [replicate, pattern]; None or no replicates frees them."""
+        if W is None or len(W) == 0:
+            self._rell_R = 0
+            self._chk(self.lib.plk_set_replicate_weights(self.h, 0, None))
+            return
+        W = np.ascontiguousarray(W, dtype=np.float64)
+        if W.ndim != 2 or W.shape[1] != self.P:
+            raise ValueError("replicate weights are [replicate, pattern]")
+        self._rell_R = W.shape[0]
+        self._chk(self.lib.plk_set_replicate_weights(self.h, W.shape[0], _d(W)))
+
+    def replicate_sums(self, first_row: int, n_rows: int, want_abs: bool = False):
+        """plk_replicate_sums: G [replicate, row] = sum_p W[r, p] row[first_row + m, p]; with
+        want_abs also Gabs, the same sum of absolute values (returned as a pair)."""
+        R = max(getattr(self, "_rell_R", 0), 1)
+        G = np.empty((R, max(int(n_rows), 1)))
+        Ga = np.empty_like(G) if want_abs else None
+        self._chk(self.lib.plk_replicate_sums(self.h, int(first_row), int(n_rows), _d(G), _d(Ga) if want_abs else None))
+        return (G, Ga) if want_abs else G
+
+    def replicate_passes(self) -> int:
+        n = ct.c_int64(0)
+        self._chk(self.lib.plk_replicate_passes(self.h, ct.byref(n)))
+        return n.value
 
     def set_timing(self, on: bool):
         self._chk(self.lib.plk_set_timing(self.h, (PLK_TIME_PARTIALS | PLK_TIME_PMAT | PLK_TIME_ROOT) if on is True

@@ -469,6 +469,60 @@ int plk_nni_scores(plk_handle h, int n_moves, const int32_t* son, const int32_t*
  * included). */
 int plk_nni_passes(plk_handle h, int64_t* passes);
 
+/* RELL resampling (resampling of estimated log-likelihoods): per-pattern log-likelihood rows kept
+ * on the device, replicate weights, and the product of the two.  Replaces the triple host loop of
+ * PairedSiteLikelihoods::computeExpectedLikelihoodWeights (Likelihood/PairedSiteLikelihoods.cpp:
+ * 124-176; the counts of ::bootstrap, :178-188): Y += lnL[model][site] * count[site] for every
+ * replicate and model is G = W . L^T.
+ *
+ * A site row is a device vector of n_patterns doubles (padding 0.0).  Rows belong to the handle
+ * and are numbered from 0.  plk_site_rows_reserve allocates n_rows of them, all 0.0 (the rows of
+ * an earlier reservation are lost); 0 frees them.  PLK_ERR_OOM, PLK_ERR_ARG for n_rows < 0.
+ * plk_site_row_set / _get move n_patterns host values (a multi-device handle scatters / gathers by
+ * shard); PLK_ERR_ARG for a row that is not reserved, here and in every call below. */
+int plk_site_rows_reserve(plk_handle h, int n_rows);
+int plk_site_row_set(plk_handle h, int row, const double* v /* n_patterns */);
+int plk_site_row_get(plk_handle h, int row, double* v /* n_patterns */);
+/* The row receives what plk_root_loglik returns in site_lnl for the current partials: the same
+ * kernels, the same values bitwise (scale counts included), nothing through the host.  A
+ * non-finite value (an underflowed pattern) is stored as 0.0 and counted in *n_bad (nullable),
+ * the rule of posteriors, mapping and NNI.  Leaves plk_kernel_path, plk_root_underflow and the
+ * next plk_root_loglik as they were.  Errors of plk_root_loglik; PLK_ERR_UNSUPPORTED under a
+ * communicator. */
+int plk_site_row_from_root(plk_handle h, int root, int row, int64_t* n_bad);
+/* Row first_row + i receives log rho_i(t_i) per pattern for the move (son[i], uncle[i]): exactly
+ * the terms plk_nni_scores weights and sums into delta at max_iter == 0, t0 = t (the same
+ * coefficient build, the same short-length expm1 form under the same condition); a pattern whose
+ * l_cur or rho is not a positive finite number gets 0.0.  So lnL_site(swapped tree, branch p of
+ * length t_i) = lnL_site(current tree) + row.  Preconditions, error codes, the reuse of an
+ * up-to-date preorder pass, the staging bound (2 GiB, PLK_TUNE NNI_CAP_KB) and multi-device
+ * behaviour are those of plk_nni_scores; t_i must be positive and finite (PLK_ERR_ARG). */
+int plk_nni_site_rows(plk_handle h, int n_moves, const int32_t* son, const int32_t* uncle,
+                      const int32_t* model /* n_moves, or NULL: model 0 */, const double* t /* n_moves */,
+                      int first_row);
+/* R replicates of per-pattern weights, replicate-major (R x n_patterns), copied to the device
+ * (padding 0.0); R == 0 frees them.  Any finite weights: integer counts are the bootstrap,
+ * Dirichlet weights the Bayesian bootstrap.  Independent of plk_set_pattern_weights and read by
+ * plk_replicate_sums only. */
+int plk_set_replicate_weights(plk_handle h, int R, const double* W /* R x n_patterns */);
+/* G[r][m] = sum_p W[r][p] row[first_row + m][p]; Gabs (nullable) the same sum of |W| |row|, the
+ * scale a rounding bound is stated in (|G - exact| <= n_patterns 2^-53 Gabs for any order).
+ * Summation rule: per plk_block_size() patterns a partial starts from +0.0 and takes the block's
+ * patterns by fused multiply-add -- 32-pattern segments ascending, inside a segment q = 0..7,
+ * inside q the patterns 32 seg + 8 k + q, k = 0..3 (one v_mfma_f64_16x16x4f64 per q) -- and the
+ * partials of an element are added in global block order, one chain from +0.0.  A multi-device
+ * handle forms the partials on all shards side by side and runs the chains shard after shard, each
+ * seeded with the shard before.  So sharding, the chunking of replicates and rows that bounds
+ * the staging (2 GiB; PLK_TUNE RELL_CAP_KB lowers it) and the place of a replicate or row in the
+ * call change no bit of any element.  PLK_ERR_STATE without weights or rows, PLK_ERR_ARG for a
+ * row range outside the reserved rows, PLK_ERR_UNSUPPORTED under a communicator or for more than
+ * 65535 pattern blocks (268 M patterns) on one device -- the blocks are the third grid dimension;
+ * shard a longer alignment with plk_create_multi.  Synchronises.
+ * plk_replicate_passes: the block-partial launches (per shard) of the last plk_replicate_sums. */
+int plk_replicate_sums(plk_handle h, int first_row, int n_rows, double* G /* R x n_rows */,
+                       double* Gabs /* R x n_rows, or NULL */);
+int plk_replicate_passes(plk_handle h, int64_t* launches);
+
 /* Pairwise sufficient statistics: for every listed pair of tips the table
  *   N[pair][a][b] = sum_p w_p [code of tip_a at p = a][code of tip_b at p = b],
  * ordered (a is the code at tip_a; the table of (b, a) is the transpose), n_codes x n_codes in the
