@@ -2637,7 +2637,7 @@ int update_levelwise(plk_handle h, const plk_op* ops, int n_ops) {
     std::memset(&k, 0, sizeof(k));
     k.parent = o.parent - h->n_tips;
     k.n = o.n_children;
-    k.flags = o.flags;
+    k.flags = o.flags & PLK_OP_ACCUMULATE;  // (kOpSigned is the library's own)
     for (int j = 0; j < o.n_children; ++j) {
       const int c = o.child[j];
       k.branch[j] = c;
@@ -3229,7 +3229,7 @@ int path_derivatives(plk_handle h, int branch, double* d1, double* d2) {
         KOp op;
         std::memset(&op, 0, sizeof(op));
         op.parent = out;
-        op.flags = k0 == 0 ? 0 : PLK_OP_ACCUMULATE;
+        op.flags = (k0 == 0 ? 0 : PLK_OP_ACCUMULATE) | kOpSigned;  // dL, d2L: either sign
         for (size_t k = k0; k < ks.size() && k < k0 + 3; ++k) {
           const int c = ks[k], j = op.n++;
           if (c == path && path == branch) {        // the differentiated branch
@@ -3356,7 +3356,7 @@ int root_pair_derivatives(plk_handle h, int a, int b, double alpha, double beta,
       KOp op;
       std::memset(&op, 0, sizeof(op));
       op.parent = slot0 + v;
-      op.flags = k0 == 0 ? 0 : PLK_OP_ACCUMULATE;
+      op.flags = (k0 == 0 ? 0 : PLK_OP_ACCUMULATE) | kOpSigned;  // substituted products: either sign
       for (size_t k = k0; k < ks.size() && k < k0 + 3; ++k) {
         const int c = ks[k], j = op.n++;
         const int x = c == a ? sub[v][0] : c == b ? sub[v][1] : -1;

@@ -37,8 +37,16 @@ struct KOp {
   int32_t child[3];  // tip index (is_tip) or internal slot
   int32_t branch[3]; // node index of the child = transition-matrix index
   int32_t is_tip[3];
-  int32_t flags;     // PLK_OP_ACCUMULATE
+  int32_t flags;     // PLK_OP_ACCUMULATE | kOpSigned
 };
+// Internal op flag: the vector being formed may have either sign (dP / d2P substituted on a
+// branch: the path and root-pair derivative vectors), so the rescale decision takes the largest
+// magnitude.  By the largest value a vector whose entries are all negative is never rescaled --
+// and a path vector stays all negative from there to the root (P and the siblings' products are
+// positive) until it leaves the double range.  Likelihood vectors keep the largest value: the
+// decision the oracle restates.
+constexpr int kOpSigned = 2;
+__device__ __forceinline__ double scale_key(double v, bool sg) { return sg ? fabs(v) : v; }
 
 struct PartialsArgs {
   double* partials;          // [n_internal][slot_stride]
@@ -143,13 +151,14 @@ __global__ __launch_bounds__(256) void partials_s4_kernel(const KOp* __restrict_
   }
 
   if (SCALE) {
+    const bool sg = (op.flags & kOpSigned) != 0;
     double m0 = 0.0, m1 = 0.0;
 #pragma unroll
     for (int c = 0; c < C; ++c)
 #pragma unroll
       for (int x = 0; x < S; ++x) {
-        m0 = fmax(m0, acc[c][x].x);
-        m1 = fmax(m1, acc[c][x].y);
+        m0 = fmax(m0, scale_key(acc[c][x].x, sg));
+        m1 = fmax(m1, scale_key(acc[c][x].y, sg));
       }
     const bool r0 = (m0 > 0.0 && m0 < kScaleThr), r1 = (m1 > 0.0 && m1 < kScaleThr);
     if (r0 || r1) {
@@ -411,6 +420,7 @@ __global__ __launch_bounds__(256) void partials_generic_kernel(const KOp* __rest
   for (int k = 0; k < n; ++k)
     if (op.is_tip[k]) code[k] = a.codes[(size_t)op.child[k] * a.n_pad + pidx];
 
+  const bool sg = (op.flags & kOpSigned) != 0;
   double m = 0.0;
   for (int c = 0; c < C; ++c) {
     for (int x0 = 0; x0 < S; x0 += XB) {
@@ -448,7 +458,7 @@ __global__ __launch_bounds__(256) void partials_generic_kernel(const KOp* __rest
       }
 #pragma unroll
       for (int xb = 0; xb < XB; ++xb) {
-        if (SCALE) m = fmax(m, acc[xb]);
+        if (SCALE) m = fmax(m, scale_key(acc[xb], sg));
         outp[(size_t)(c * S + x0 + xb) * kTile] = acc[xb];
       }
     }
@@ -500,6 +510,7 @@ __global__ __launch_bounds__(256) void partials_sgpr_kernel(const KOp* __restric
     for (int k = 0; k < n; ++k)
       if (!op.is_tip[k]) cnt += a.scale[(size_t)op.child[k] * a.n_pad + pidx];
   }
+  const bool sg = (op.flags & kOpSigned) != 0;
   double m = 0.0;
   for (int c = 0; c < C; ++c) {
     double acc[S];
@@ -532,7 +543,7 @@ __global__ __launch_bounds__(256) void partials_sgpr_kernel(const KOp* __restric
     }
 #pragma unroll
     for (int x = 0; x < S; ++x) {
-      if (SCALE) m = fmax(m, acc[x]);
+      if (SCALE) m = fmax(m, scale_key(acc[x], sg));
       outp[(size_t)(c * S + x) * kTile] = acc[x];
     }
   }

@@ -53,6 +53,7 @@ __global__ __launch_bounds__(kM64Threads) void partials_mfma64_kernel(const KOp*
     for (int k = 0; k < n; ++k)
       if (!op.is_tip[k]) cnt += a.scale[(size_t)op.child[k] * a.n_pad + pidx];
   }
+  const bool sg = (op.flags & kOpSigned) != 0;
   double m = 0.0;
 
   for (int c = 0; c < C; ++c) {
@@ -109,7 +110,7 @@ __global__ __launch_bounds__(kM64Threads) void partials_mfma64_kernel(const KOp*
     for (int xt = 0; xt < 4; ++xt)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        if (SCALE) m = fmax(m, acc[xt][r]);
+        if (SCALE) m = fmax(m, scale_key(acc[xt][r], sg));
         outp[(size_t)(c * S + 16 * xt + lr + 4 * r) * kTile] = acc[xt][r];
       }
   }

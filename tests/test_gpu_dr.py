@@ -4,7 +4,8 @@ PLK_FLAG_DOUBLE_RECURSIVE) -- the reference's DRHomogeneousTreeLikelihood
 
 Checked against
   - the single-traversal path derivatives of the same engine (plk_branch_derivatives,
-    themselves checked against central differences of the oracle in test_gpu_parity.py):
+    themselves checked against central differences of the oracle in test_gpu_parity.py, and
+    analytically, as the DR pass is, against the extended-range reference in test_gpu_xref.py):
     relative 1e-10 on d1 and d2 (the reference's own R-vs-DR check is 1e-6 absolute,
     test/test_likelihood.cpp:122-135);
   - central differences of the CPU oracle for a few branches.
