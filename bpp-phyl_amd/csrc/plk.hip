@@ -1034,10 +1034,11 @@ int multi_evaluate(plk_handle h, int n, const int32_t* branch, const int32_t* mo
   return PLK_OK;
 }
 
-// per-shard values summed in shard order (the order of the former one-thread loop)
-int multi_branch_derivatives(plk_handle h, int branch, double* d1, double* d2) {
+// a pair of values per shard (f's outputs), summed in shard order (the order of the former
+// one-thread loop)
+int multi_sum_pair(plk_handle h, const std::function<int(plk_handle, double*, double*)>& f, double* d1, double* d2) {
   std::vector<double> a(h->shards.size()), b(h->shards.size());
-  const int rc = multi_run(h, [&](size_t i) { return plk_branch_derivatives(h->shards[i], branch, &a[i], &b[i]); });
+  const int rc = multi_run(h, [&](size_t i) { return f(h->shards[i], &a[i], &b[i]); });
   if (rc) return rc;
   double s1 = 0.0, s2 = 0.0;
   for (size_t i = 0; i < a.size(); ++i) {
@@ -2162,6 +2163,21 @@ void fill_common_args(plk_handle h, int32_t* uflow, Args& a) {
   a.uflow = uflow;
 }
 
+// The levelwise kernels' argument block, from the handle
+PartialsArgs partials_args(plk_handle h) {
+  PartialsArgs a;
+  a.partials = h->partials;
+  a.scale = h->scale;
+  a.codes = h->codes;
+  a.tipP = h->tipP;
+  a.pmats = h->pmats;
+  a.slot_stride = h->slot_stride;
+  a.n_pad = h->n_pad;
+  a.n_tiles = h->n_tiles;
+  a.n_codes = h->n_codes;
+  return a;
+}
+
 // The interpreters' argument block (frag_start is set per tier); returns tree4_kernel's LDS bytes
 size_t tree_args(plk_handle h, TreeArgs& a) {
   fill_common_args(h, h->prog_root >= 0 ? uflow_arm(h) : nullptr, a);
@@ -2654,16 +2670,7 @@ int update_levelwise(plk_handle h, const plk_op* ops, int n_ops) {
   h->last_level_start = level_start;
   }
 
-  PartialsArgs a;
-  a.partials = h->partials;
-  a.scale = h->scale;
-  a.codes = h->codes;
-  a.tipP = h->tipP;
-  a.pmats = h->pmats;
-  a.slot_stride = h->slot_stride;
-  a.n_pad = h->n_pad;
-  a.n_tiles = h->n_tiles;
-  a.n_codes = h->n_codes;
+  const PartialsArgs a = partials_args(h);
   const bool s4 = (h->S == 4 && s4_supported(h->C) && h->n_codes <= kMaxCodes4);
   for (int l = 0; l <= max_level; ++l) {
     const int cnt = level_start[l + 1] - level_start[l];
@@ -2949,16 +2956,7 @@ int update_compressed(plk_handle h, const plk_op* ops, int n_ops) {
   }
   int rc = refresh_tip_tables(h);
   if (rc) return rc;
-  PartialsArgs a;
-  a.partials = h->partials;
-  a.scale = h->scale;
-  a.codes = h->codes;
-  a.tipP = h->tipP;
-  a.pmats = h->pmats;
-  a.slot_stride = h->slot_stride;
-  a.n_pad = h->n_pad;
-  a.n_tiles = h->n_tiles;
-  a.n_codes = h->n_codes;
+  const PartialsArgs a = partials_args(h);
   const int L = (int)h->cmp_level_start.size() - 1;
   for (int l = 0; l < L; ++l) {
     const int cnt = h->cmp_level_start[l + 1] - h->cmp_level_start[l];
@@ -2997,16 +2995,7 @@ int update_compressed(plk_handle h, const plk_op* ops, int n_ops) {
 // tip row with its codes and table); the path vectors ping-pong between scratch slots.
 // ---------------------------------------------------------------------------
 int launch_partials_ops(plk_handle h, const KOp* d_ops, int n_ops) {
-  PartialsArgs a;
-  a.partials = h->partials;
-  a.scale = h->scale;
-  a.codes = h->codes;
-  a.tipP = h->tipP;
-  a.pmats = h->pmats;
-  a.slot_stride = h->slot_stride;
-  a.n_pad = h->n_pad;
-  a.n_tiles = h->n_tiles;
-  a.n_codes = h->n_codes;
+  const PartialsArgs a = partials_args(h);
   if (h->S == 4 && s4_supported(h->C) && h->n_codes <= kMaxCodes4) {
     if (h->flags & PLK_FLAG_SCALING)
       launch_s4<true>(h, d_ops, n_ops, a);
@@ -3020,8 +3009,124 @@ int launch_partials_ops(plk_handle h, const KOp* d_ops, int n_ops) {
   return PLK_OK;
 }
 
-int materialize_last_traversal(plk_handle h);
-void topo_postorder(plk_handle h, int root, std::vector<plk_op>& ops);
+// A flat op list (plk_topo.hpp) into d_ops.  `sync`: wait for the copy, which reads `flat`.
+int upload_ops(plk_handle h, const std::vector<KOp>& flat, bool sync) {
+  int rc = ensure_cap(h, (void**)&h->d_ops, &h->d_ops_cap, flat.size() * sizeof(KOp));
+  if (rc) return rc;
+  HIPCHK(h, hipMemcpyAsync(h->d_ops, flat.data(), flat.size() * sizeof(KOp), hipMemcpyHostToDevice, h->stream));
+  if (sync) HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->last_ops.clear();  // d_ops now holds these ops, not the levelwise traversal's
+  return PLK_OK;
+}
+
+// An op list is fusable when every ACCUMULATE op continues the node of the op
+// just before it (the polytomy split produced by the host) -- then the program
+// treats the node as one multi-child node.
+bool fusable(const plk_op* ops, int n_ops) {
+  for (int i = 0; i < n_ops; ++i)
+    if ((ops[i].flags & PLK_OP_ACCUMULATE) && (i == 0 || ops[i - 1].parent != ops[i].parent)) return false;
+  return true;
+}
+
+// The traversal that serves an op list: per-subtree compression where the handle asks for it
+// (unless the caller wants full-length slots), else the fused traversal, else level by level.
+int update_any(plk_handle h, const plk_op* ops, int n_ops, bool compressed = true) {
+  if (compressed && (h->flags & PLK_FLAG_SUBTREE_PATTERNS)) return update_compressed(h, ops, n_ops);
+  if (tree4_supported(h) && fusable(ops, n_ops)) return update_tree4(h, ops, n_ops);
+  return update_levelwise(h, ops, n_ops);
+}
+
+// Postorder op list of the merged topology below `root` (<= 3 children per op; a
+// polytomy continues with ACCUMULATE ops), as the host would hand it over.
+void topo_postorder(plk_handle h, int root, std::vector<plk_op>& ops) {
+  std::vector<std::pair<int, size_t> > st(1, std::make_pair(root, (size_t)0));
+  while (!st.empty()) {
+    const int n = st.back().first;
+    const std::vector<int>& ks = h->topo_kids[n];
+    if (st.back().second < ks.size()) {
+      const int c = ks[st.back().second++];
+      if (c >= h->n_tips) st.push_back(std::make_pair(c, (size_t)0));
+      continue;
+    }
+    for (size_t k0 = 0; k0 < ks.size(); k0 += 3) {
+      plk_op o;
+      std::memset(&o, 0, sizeof(o));
+      o.parent = n;
+      o.flags = k0 == 0 ? 0 : PLK_OP_ACCUMULATE;
+      for (size_t k = k0; k < ks.size() && k < k0 + 3; ++k) o.child[o.n_children++] = ks[k];
+      ops.push_back(o);
+    }
+    st.pop_back();
+  }
+}
+
+// Re-run the traversal of the whole (merged) tree writing every partial (same arithmetic,
+// identical values).
+int materialize_last_traversal(plk_handle h) {
+  std::vector<plk_op> ops;
+  topo_postorder(h, TopoView(h->topo_kids, h->trav_ops.back().parent).root, ops);
+  const unsigned saved = h->flags;
+  h->flags &= ~(unsigned)PLK_FLAG_LNL_ONLY;
+  const int rc = update_any(h, ops.data(), (int)ops.size(), false);
+  h->flags = saved;
+  if (!rc && (h->flags & PLK_FLAG_SUBTREE_PATTERNS)) h->slots_expanded = true;
+  return rc;
+}
+
+// Every partial of `nodes` (tips skipped) in HBM at full length: materialise the whole tree
+// once if one is missing, or if a compressed traversal's slots still hold distinct subtree
+// patterns (expanded once, until the next compressed traversal).
+int ensure_partials(plk_handle h, const std::vector<int>& nodes) {
+  bool need = (h->flags & PLK_FLAG_SUBTREE_PATTERNS) && !h->slots_expanded;
+  for (int n : nodes)
+    if (n >= h->n_tips && !h->materialized[n - h->n_tips]) need = true;
+  return need ? materialize_last_traversal(h) : PLK_OK;
+}
+
+// src (dpmats or d2pmats) of `branch` into scratch matrix x; for a tip branch also its codes
+// into scratch tip row x, with that matrix's table
+int substitute_branch(plk_handle h, const double* src, int branch, int x) {
+  const int C = h->C, S = h->S, nc = h->n_codes, sm = h->n_nodes + x, st = h->n_tips + x;
+  const size_t PS = (size_t)C * S * S;
+  HIPCHK(h, hipMemcpyAsync(h->pmats + (size_t)sm * PS, src + (size_t)branch * PS, PS * sizeof(double),
+                           hipMemcpyDeviceToDevice, h->stream));
+  if (branch < h->n_tips) {
+    HIPCHK(h, hipMemcpyAsync(h->codes + (size_t)st * h->n_pad, h->codes + (size_t)branch * h->n_pad, (size_t)h->n_pad,
+                             hipMemcpyDeviceToDevice, h->stream));
+    tip_table_kernel<<<dim3(1, C), 256, 0, h->stream>>>(h->pmats + (size_t)sm * PS, h->code_table,
+                                                        h->tipP + (size_t)st * C * nc * S, 1, C, S, nc);
+    HIPCHK(h, hipGetLastError());
+  }
+  h->pmatsT_dirty = true;  // S = 64 kernels read the transposed copy, scratch included
+  return PLK_OK;
+}
+
+// d1_sums / d2_sums: one value per wave of a derivative reduction, allocated on first use ...
+int ensure_wave_sums(plk_handle h) {
+  int rc;
+  if (!h->d1_sums) {
+    if ((rc = dalloc(h, (void**)&h->d1_sums, (size_t)(h->n_pad / 64) * sizeof(double)))) return rc;
+    if ((rc = dalloc(h, (void**)&h->d2_sums, (size_t)(h->n_pad / 64) * sizeof(double)))) return rc;
+  }
+  return PLK_OK;
+}
+
+// ... and summed on the host in wave order (the same order for any run)
+int read_wave_sums(plk_handle h, double* d1, double* d2) {
+  const int n_waves = (int)((h->n_patterns + 63) / 64);
+  std::vector<double> w1(n_waves), w2(n_waves);
+  HIPCHK(h, hipMemcpyAsync(w1.data(), h->d1_sums, n_waves * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(w2.data(), h->d2_sums, n_waves * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  double s1 = 0.0, s2 = 0.0;
+  for (int i = 0; i < n_waves; ++i) {
+    s1 += w1[i];
+    s2 += w2[i];
+  }
+  if (d1) *d1 = s1;
+  if (d2) *d2 = s2;
+  return PLK_OK;
+}
 
 // plk_traversal_work: the program that served the last traversal, walked on the host.
 void traversal_work(plk_handle h, plk_work* w) {
@@ -3176,98 +3281,26 @@ int path_derivatives(plk_handle h, int branch, double* d1, double* d2) {
   if (!h->pi_set || !h->rates_set) return fail(h, PLK_ERR_STATE, "root frequencies / category rates not set");
   hipSetDevice(h->device);
   const int nt = h->n_tips;
-  std::vector<std::vector<int> > kids(h->n_nodes);
-  std::vector<int> parent(h->n_nodes, -1);
-  // the merged tree of every traversal so far (an incremental call lists only the
-  // ancestors of the changed branches)
-  for (int n = 0; n < h->n_nodes; ++n)
-    for (int c : h->topo_kids[n]) {
-      kids[n].push_back(c);
-      parent[c] = n;
-    }
-  if (parent[branch] < 0) return fail(h, PLK_ERR_ARG, "branch %d is not below any node of the last traversal", branch);
-  int root = parent[branch];
-  while (parent[root] >= 0) root = parent[root];
-  // a compressed traversal's slots hold distinct subtree patterns: expand once
-  bool need = !h->materialized[root - nt] || ((h->flags & PLK_FLAG_SUBTREE_PATTERNS) && !h->slots_expanded);
-  for (int n = parent[branch]; n >= 0; n = parent[n])
-    for (int c : kids[n])
-      if (c >= nt && !h->materialized[c - nt]) need = true;
-  if (need) {
-    int rc = materialize_last_traversal(h);
-    if (rc) return rc;
-  }
-  int rc = refresh_tip_tables(h);
-  if (rc) return rc;
-  const int C = h->C, S = h->S, nc = h->n_codes;
-  const size_t PS = (size_t)C * S * S;
+  const TopoView t(h->topo_kids, branch);
+  if (t.parent[branch] < 0) return fail(h, PLK_ERR_ARG, "branch %d is not below any node of the last traversal", branch);
+  std::vector<int> read = t.path_sons(branch);
+  read.push_back(t.root);
+  int rc;
+  if ((rc = ensure_partials(h, read))) return rc;
+  if ((rc = refresh_tip_tables(h))) return rc;
   const int sb[2] = {h->n_nodes, h->n_nodes + 1};     // scratch transition matrices (dP_b, d2P_b)
   const int st[2] = {nt, nt + 1};                     // scratch tip rows
   const int slot0 = h->n_internal;                    // scratch slots: pass x uses slot0 + 2x, +1
-  const double* src[2] = {h->dpmats, h->d2pmats};
-  for (int x = 0; x < 2; ++x) {
-    HIPCHK(h, hipMemcpyAsync(h->pmats + (size_t)sb[x] * PS, src[x] + (size_t)branch * PS, PS * sizeof(double),
-                             hipMemcpyDeviceToDevice, h->stream));
-    if (branch < nt) {
-      HIPCHK(h, hipMemcpyAsync(h->codes + (size_t)st[x] * h->n_pad, h->codes + (size_t)branch * h->n_pad,
-                               (size_t)h->n_pad, hipMemcpyDeviceToDevice, h->stream));
-      tip_table_kernel<<<dim3(1, C), 256, 0, h->stream>>>(h->pmats + (size_t)sb[x] * PS, h->code_table,
-                                                          h->tipP + (size_t)st[x] * C * nc * S, 1, C, S, nc);
-      HIPCHK(h, hipGetLastError());
-    }
-  }
-  h->pmatsT_dirty = true;  // S = 64 kernels read the transposed copy, scratch included
-  // one launch per (path node, child chunk): both passes side by side
-  std::vector<std::vector<KOp> > launches;
-  int path = branch, cur = 0;
-  for (int n = parent[branch]; n >= 0; path = n, n = parent[n]) {
-    std::vector<KOp> chunk[2];
-    for (int x = 0; x < 2; ++x) {
-      const int out = slot0 + 2 * x + (cur & 1), in = slot0 + 2 * x + ((cur + 1) & 1);
-      const std::vector<int>& ks = kids[n];
-      for (size_t k0 = 0; k0 < ks.size(); k0 += 3) {
-        KOp op;
-        std::memset(&op, 0, sizeof(op));
-        op.parent = out;
-        op.flags = (k0 == 0 ? 0 : PLK_OP_ACCUMULATE) | kOpSigned;  // dL, d2L: either sign
-        for (size_t k = k0; k < ks.size() && k < k0 + 3; ++k) {
-          const int c = ks[k], j = op.n++;
-          if (c == path && path == branch) {        // the differentiated branch
-            op.is_tip[j] = c < nt;
-            op.child[j] = c < nt ? st[x] : c - nt;
-            op.branch[j] = sb[x];
-          } else if (c == path) {                   // the path vector from the step below
-            op.is_tip[j] = 0;
-            op.child[j] = in;
-            op.branch[j] = c;
-          } else {
-            op.is_tip[j] = c < nt;
-            op.child[j] = c < nt ? c : c - nt;
-            op.branch[j] = c;
-          }
-        }
-        chunk[x].push_back(op);
-      }
-    }
-    for (size_t j = 0; j < chunk[0].size(); ++j) launches.push_back({chunk[0][j], chunk[1][j]});
-    ++cur;
-  }
+  if ((rc = substitute_branch(h, h->dpmats, branch, 0))) return rc;
+  if ((rc = substitute_branch(h, h->d2pmats, branch, 1))) return rc;
   std::vector<KOp> flat;
-  for (auto& l : launches) flat.insert(flat.end(), l.begin(), l.end());
-  rc = ensure_cap(h, (void**)&h->d_ops, &h->d_ops_cap, flat.size() * sizeof(KOp));
-  if (rc) return rc;
-  HIPCHK(h, hipMemcpyAsync(h->d_ops, flat.data(), flat.size() * sizeof(KOp), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  h->last_ops.clear();  // d_ops now holds these ops, not the levelwise traversal's
-  for (size_t l = 0; l < launches.size(); ++l) {
-    rc = launch_partials_ops(h, h->d_ops + 2 * l, 2);
-    if (rc) return rc;
-  }
-  const int last = (cur - 1) & 1;
-  if (!h->d1_sums) {
-    if ((rc = dalloc(h, (void**)&h->d1_sums, (size_t)(h->n_pad / 64) * sizeof(double)))) return rc;
-    if ((rc = dalloc(h, (void**)&h->d2_sums, (size_t)(h->n_pad / 64) * sizeof(double)))) return rc;
-  }
+  std::vector<OpLaunch> launches;
+  const int last = (path_ops(t, branch, nt, st, sb, slot0, flat, launches) - 1) & 1;
+  if ((rc = upload_ops(h, flat, true))) return rc;
+  for (const OpLaunch& l : launches)
+    if ((rc = launch_partials_ops(h, h->d_ops + l.first, l.count))) return rc;
+  if ((rc = ensure_wave_sums(h))) return rc;
+  const int root = t.root;
   DRArgs a;
   a.L = h->partials + (size_t)(root - nt) * h->slot_stride;
   a.dL = h->partials + (size_t)(slot0 + last) * h->slot_stride;
@@ -3282,24 +3315,12 @@ int path_derivatives(plk_handle h, int branch, double* d1, double* d2) {
   a.d1_sums = h->d1_sums;
   a.d2_sums = h->d2_sums;
   a.n_patterns = h->n_patterns;
-  a.S = S;
-  a.C = C;
+  a.S = h->S;
+  a.C = h->C;
   a.guard = (h->flags & PLK_FLAG_NONNEG_GUARD) ? 1 : 0;
   deriv_reduce_kernel<<<(unsigned)(h->n_pad / 256), 256, 0, h->stream>>>(a);
   HIPCHK(h, hipGetLastError());
-  const int n_waves = (int)((h->n_patterns + 63) / 64);
-  std::vector<double> w1(n_waves), w2(n_waves);
-  HIPCHK(h, hipMemcpyAsync(w1.data(), h->d1_sums, n_waves * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(w2.data(), h->d2_sums, n_waves * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  double s1 = 0.0, s2 = 0.0;
-  for (int i = 0; i < n_waves; ++i) {
-    s1 += w1[i];
-    s2 += w2[i];
-  }
-  if (d1) *d1 = s1;
-  if (d2) *d2 = s2;
-  return PLK_OK;
+  return read_wave_sums(h, d1, d2);
 }
 
 // plk_root_pair_derivatives: the five root products with dP / d2P substituted on the two
@@ -3315,67 +3336,28 @@ int root_pair_derivatives(plk_handle h, int a, int b, double alpha, double beta,
   if (h->trav_ops.empty()) return fail(h, PLK_ERR_STATE, "no traversal yet (plk_update_partials)");
   hipSetDevice(h->device);
   const int nt = h->n_tips;
-  std::vector<int> parent(h->n_nodes, -1);
-  for (int n = 0; n < h->n_nodes; ++n)
-    for (int c : h->topo_kids[n]) parent[c] = n;
-  const int root = parent[a];
-  if (root < 0 || parent[b] != root || parent[root] >= 0)
+  const TopoView t(h->topo_kids, a);
+  const int root = t.parent[a];
+  if (root < 0 || t.parent[b] != root || t.parent[root] >= 0)
     return fail(h, PLK_ERR_ARG, "branches %d and %d are not both sons of the traversal's root", a, b);
-  const std::vector<int>& ks = h->topo_kids[root];
-  bool need = !h->materialized[root - nt] || ((h->flags & PLK_FLAG_SUBTREE_PATTERNS) && !h->slots_expanded);
-  for (int c : ks)
-    if (c >= nt && !h->materialized[c - nt]) need = true;
+  std::vector<int> read = t.kids[root];
+  read.push_back(root);
   int rc;
-  if (need && (rc = materialize_last_traversal(h))) return rc;
+  if ((rc = ensure_partials(h, read))) return rc;
   if ((rc = refresh_tip_tables(h))) return rc;
-  const int C = h->C, S = h->S, nc = h->n_codes;
-  const size_t PS = (size_t)C * S * S;
   // scratch matrices / tip rows: 0 dP_a, 1 d2P_a, 2 dP_b, 3 d2P_b
   const int son[4] = {a, a, b, b};
   const double* src[4] = {h->dpmats, h->d2pmats, h->dpmats, h->d2pmats};
-  for (int x = 0; x < 4; ++x) {
-    const int sm = h->n_nodes + x, st = nt + x;
-    HIPCHK(h, hipMemcpyAsync(h->pmats + (size_t)sm * PS, src[x] + (size_t)son[x] * PS, PS * sizeof(double),
-                             hipMemcpyDeviceToDevice, h->stream));
-    if (son[x] < nt) {
-      HIPCHK(h, hipMemcpyAsync(h->codes + (size_t)st * h->n_pad, h->codes + (size_t)son[x] * h->n_pad,
-                               (size_t)h->n_pad, hipMemcpyDeviceToDevice, h->stream));
-      tip_table_kernel<<<dim3(1, C), 256, 0, h->stream>>>(h->pmats + (size_t)sm * PS, h->code_table,
-                                                          h->tipP + (size_t)st * C * nc * S, 1, C, S, nc);
-      HIPCHK(h, hipGetLastError());
-    }
-  }
-  h->pmatsT_dirty = true;
-  // variant v: scratch index substituted on a and on b (-1 = the son's own P)
-  const int sub[5][2] = {{0, -1}, {-1, 2}, {1, -1}, {-1, 3}, {0, 2}};
+  for (int x = 0; x < 4; ++x)
+    if ((rc = substitute_branch(h, src[x], son[x], x))) return rc;
   const int slot0 = h->n_internal;
   std::vector<KOp> flat;
-  const size_t n_chunks = (ks.size() + 2) / 3;
-  for (size_t k0 = 0; k0 < ks.size(); k0 += 3)
-    for (int v = 0; v < 5; ++v) {
-      KOp op;
-      std::memset(&op, 0, sizeof(op));
-      op.parent = slot0 + v;
-      op.flags = (k0 == 0 ? 0 : PLK_OP_ACCUMULATE) | kOpSigned;  // substituted products: either sign
-      for (size_t k = k0; k < ks.size() && k < k0 + 3; ++k) {
-        const int c = ks[k], j = op.n++;
-        const int x = c == a ? sub[v][0] : c == b ? sub[v][1] : -1;
-        op.is_tip[j] = c < nt;
-        op.child[j] = c < nt ? (x >= 0 ? nt + x : c) : c - nt;
-        op.branch[j] = x >= 0 ? h->n_nodes + x : c;
-      }
-      flat.push_back(op);
-    }
-  if ((rc = ensure_cap(h, (void**)&h->d_ops, &h->d_ops_cap, flat.size() * sizeof(KOp)))) return rc;
-  HIPCHK(h, hipMemcpyAsync(h->d_ops, flat.data(), flat.size() * sizeof(KOp), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  h->last_ops.clear();  // d_ops now holds these ops, not the levelwise traversal's
-  for (size_t l = 0; l < n_chunks; ++l)
-    if ((rc = launch_partials_ops(h, h->d_ops + 5 * l, 5))) return rc;
-  if (!h->d1_sums) {
-    if ((rc = dalloc(h, (void**)&h->d1_sums, (size_t)(h->n_pad / 64) * sizeof(double)))) return rc;
-    if ((rc = dalloc(h, (void**)&h->d2_sums, (size_t)(h->n_pad / 64) * sizeof(double)))) return rc;
-  }
+  std::vector<OpLaunch> launches;
+  root_pair_ops(t, root, a, b, nt, h->n_nodes, slot0, flat, launches);
+  if ((rc = upload_ops(h, flat, true))) return rc;
+  for (const OpLaunch& l : launches)
+    if ((rc = launch_partials_ops(h, h->d_ops + l.first, l.count))) return rc;
+  if ((rc = ensure_wave_sums(h))) return rc;
   const bool sc = (h->flags & PLK_FLAG_SCALING) != 0;
   PairArgs pa;
   pa.L = h->partials + (size_t)(root - nt) * h->slot_stride;
@@ -3392,24 +3374,12 @@ int root_pair_derivatives(plk_handle h, int a, int b, double alpha, double beta,
   pa.n_patterns = h->n_patterns;
   pa.alpha = alpha;
   pa.beta = beta;
-  pa.S = S;
-  pa.C = C;
+  pa.S = h->S;
+  pa.C = h->C;
   pa.guard = (h->flags & PLK_FLAG_NONNEG_GUARD) ? 1 : 0;
   pair_reduce_kernel<<<(unsigned)(h->n_pad / 256), 256, 0, h->stream>>>(pa);
   HIPCHK(h, hipGetLastError());
-  const int n_waves = (int)((h->n_patterns + 63) / 64);
-  std::vector<double> w1(n_waves), w2(n_waves);
-  HIPCHK(h, hipMemcpyAsync(w1.data(), h->d1_sums, n_waves * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(w2.data(), h->d2_sums, n_waves * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  double s1 = 0.0, s2 = 0.0;
-  for (int i = 0; i < n_waves; ++i) {
-    s1 += w1[i];
-    s2 += w2[i];
-  }
-  if (d1) *d1 = s1;
-  if (d2) *d2 = s2;
-  return PLK_OK;
+  return read_wave_sums(h, d1, d2);
 }
 
 int validate_ops(plk_handle h, const plk_op* ops, int n_ops) {
@@ -3432,71 +3402,43 @@ int validate_ops(plk_handle h, const plk_op* ops, int n_ops) {
   return PLK_OK;
 }
 
-// An op list is fusable when every ACCUMULATE op continues the node of the op
-// just before it (the polytomy split produced by the host) -- then the program
-// treats the node as one multi-child node.
-bool fusable(const plk_op* ops, int n_ops) {
-  for (int i = 0; i < n_ops; ++i)
-    if ((ops[i].flags & PLK_OP_ACCUMULATE) && (i == 0 || ops[i - 1].parent != ops[i].parent)) return false;
-  return true;
-}
-
-// Re-run the traversal of the whole (merged) tree writing every partial (same arithmetic,
-// identical values).
-int materialize_last_traversal(plk_handle h) {
-  std::vector<int> parent(h->n_nodes, -1);
-  for (int n = 0; n < h->n_nodes; ++n)
-    for (int c : h->topo_kids[n]) parent[c] = n;
-  int root = h->trav_ops.back().parent;
-  while (parent[root] >= 0) root = parent[root];
-  std::vector<plk_op> ops;
-  topo_postorder(h, root, ops);
-  const unsigned saved = h->flags;
-  h->flags &= ~(unsigned)PLK_FLAG_LNL_ONLY;
-  const int rc = tree4_supported(h) && fusable(ops.data(), (int)ops.size())
-                     ? update_tree4(h, ops.data(), (int)ops.size())
-                     : update_levelwise(h, ops.data(), (int)ops.size());
-  h->flags = saved;
-  if (!rc && (h->flags & PLK_FLAG_SUBTREE_PATTERNS)) h->slots_expanded = true;
-  return rc;
-}
-
-// Postorder op list of the merged topology below `root` (<= 3 children per op; a
-// polytomy continues with ACCUMULATE ops), as the host would hand it over.
-void topo_postorder(plk_handle h, int root, std::vector<plk_op>& ops) {
-  std::vector<std::pair<int, size_t> > st(1, std::make_pair(root, (size_t)0));
-  while (!st.empty()) {
-    const int n = st.back().first;
-    const std::vector<int>& ks = h->topo_kids[n];
-    if (st.back().second < ks.size()) {
-      const int c = ks[st.back().second++];
-      if (c >= h->n_tips) st.push_back(std::make_pair(c, (size_t)0));
-      continue;
-    }
-    for (size_t k0 = 0; k0 < ks.size(); k0 += 3) {
-      plk_op o;
-      std::memset(&o, 0, sizeof(o));
-      o.parent = n;
-      o.flags = k0 == 0 ? 0 : PLK_OP_ACCUMULATE;
-      for (size_t k = k0; k < ks.size() && k < k0 + 3; ++k) o.child[o.n_children++] = ks[k];
-      ops.push_back(o);
-    }
-    st.pop_back();
-  }
-}
-
 // ---------------------------------------------------------------------------
 // Double-recursive derivatives of every branch (plk_dr.hpp; row f4):
 // DRHomogeneousTreeLikelihood::computeSubtreeLikelihoodPrefix (:543-651) as a
 // levelwise preorder pass of ordinary partial updates into the U slots, then one
 // reduction launch over all branches (computeTreeDLikelihoods / D2 twins :287-423).
 // ---------------------------------------------------------------------------
+// The DR kernels' argument block, from the handle: n_br branches, n_blk block sums each
+// (G, the classes staged in LDS at a time, is the caller's)
+DrArgs dr_args(plk_handle h, size_t n_br, int n_blk) {
+  DrArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.partials = h->partials;
+  a.codes = h->codes;
+  a.code_table = h->code_table;
+  a.pmats = h->pmats;
+  a.dpmats = h->dpmats;
+  a.d2pmats = h->d2pmats;
+  a.pi = h->pi;
+  a.probs = h->probs;
+  a.weights = h->weights;
+  a.tipP = h->tipP;
+  a.n_codes = h->n_codes;
+  a.blk1 = h->dr_blk;
+  a.blk2 = h->dr_blk + n_br * n_blk;
+  a.uout = h->partials;  // (the fused preorder writes U)
+  a.slot_stride = h->slot_stride;
+  a.n_pad = h->n_pad;
+  a.n_patterns = h->n_patterns;
+  a.C = h->C;
+  a.n_blk = n_blk;
+  return a;
+}
+
 // Row f4 for 4 states without rescaling: dr_pre_s4_kernel level by level (fathers of
 // depth d in one launch), then the fixed-order sums of the per-block branch terms.
-int dr_fused_preorder(plk_handle h, const std::vector<std::vector<int> >& depth, const std::vector<int>& parent,
-                      int root, double* d1, double* d2) {
+int dr_fused_preorder(plk_handle h, const std::vector<std::vector<int> >& depth, int root, double* d1, double* d2) {
   const int C = h->C, nt = h->n_tips, nn = h->n_nodes;
-  (void)parent;
   std::vector<DrBranch> br;  // one row per branch (dr_sum_kernel's node map)
   std::vector<int> bidx(nn, -1);
   for (size_t d = 1; d < depth.size(); ++d)
@@ -3547,27 +3489,7 @@ int dr_fused_preorder(plk_handle h, const std::vector<std::vector<int> >& depth,
   HIPCHK(h, hipMemcpyAsync(h->d_drb, br.data(), br.size() * sizeof(DrBranch), hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipMemcpyAsync(h->d_drpre, ops.data(), ops.size() * sizeof(DrPreOp), hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipMemsetAsync(h->dr_out, 0, 2 * (size_t)nn * sizeof(double), h->stream));
-  DrArgs a;
-  std::memset(&a, 0, sizeof(a));
-  a.partials = h->partials;
-  a.codes = h->codes;
-  a.code_table = h->code_table;
-  a.pmats = h->pmats;
-  a.dpmats = h->dpmats;
-  a.d2pmats = h->d2pmats;
-  a.pi = h->pi;
-  a.probs = h->probs;
-  a.weights = h->weights;
-  a.tipP = h->tipP;
-  a.n_codes = h->n_codes;
-  a.blk1 = h->dr_blk;
-  a.blk2 = h->dr_blk + br.size() * n_blk;
-  a.slot_stride = h->slot_stride;
-  a.n_pad = h->n_pad;
-  a.n_patterns = h->n_patterns;
-  a.C = C;
-  a.n_blk = n_blk;
-  a.uout = h->partials;
+  const DrArgs a = dr_args(h, br.size(), n_blk);
   TimedSpan span(h, PLK_TIME_PARTIALS, 0);
   for (const Level& l : levels) {
     const dim3 grid((unsigned)n_blk, (unsigned)l.count);
@@ -3619,39 +3541,20 @@ int dr_derivatives(plk_handle h, double* d1, double* d2) {
   if (!(S == 2 || S == 3 || S == 4 || S == 20 || S == 64))
     return fail(h, PLK_ERR_UNSUPPORTED, "state count %d has no kernel instance", S);
   hipSetDevice(h->device);
-  std::vector<int> parent(nn, -1);
-  for (int n = 0; n < nn; ++n)
-    for (int c : h->topo_kids[n]) parent[c] = n;
-  int root = h->trav_ops.back().parent;
-  while (parent[root] >= 0) root = parent[root];
+  const TopoView t(h->topo_kids, h->trav_ops.back().parent);
+  const std::vector<int>& parent = t.parent;
+  const int root = t.root;
   if (h->topo_kids[root].size() < 2) return fail(h, PLK_ERR_UNSUPPORTED, "root %d has fewer than two sons", root);
-  // preorder levels (depth 1 = sons of the root)
-  std::vector<std::vector<int> > depth(1, std::vector<int>(1, root));
-  while (true) {
-    std::vector<int> next;
-    for (int n : depth.back())
-      for (int c : h->topo_kids[n]) next.push_back(c);
-    if (next.empty()) break;
-    depth.push_back(next);
-  }
-  bool need = false;
+  const std::vector<std::vector<int> > depth = t.levels();  // (depth 1 = sons of the root)
+  std::vector<int> all;
   for (size_t d = 0; d < depth.size(); ++d)
     for (int v : depth[d]) {
       if (d > 0 && (h->deriv_valid.empty() || !h->deriv_valid[v]))
         return fail(h, PLK_ERR_STATE, "dP/d2P of branch %d not computed (PLK_DERIV_DP | PLK_DERIV_D2P)", v);
-      if (v >= nt && !h->materialized[v - nt]) need = true;
+      all.push_back(v);
     }
   int rc;
-  if (need) {  // every L_v is read from HBM: materialise the whole tree once
-    std::vector<plk_op> ops;
-    topo_postorder(h, root, ops);
-    const unsigned saved = h->flags;
-    h->flags &= ~(unsigned)PLK_FLAG_LNL_ONLY;
-    rc = tree4_supported(h) && fusable(ops.data(), (int)ops.size()) ? update_tree4(h, ops.data(), (int)ops.size())
-                                                                    : update_levelwise(h, ops.data(), (int)ops.size());
-    h->flags = saved;
-    if (rc) return rc;
-  }
+  if ((rc = ensure_partials(h, all))) return rc;  // every L_v is read from HBM
   if ((rc = refresh_tip_tables(h))) return rc;
   if ((S == 20 || S == 64) && (rc = ensure_pmatsT(h))) return rc;
   // 4 and 20 states (1, 2 or 4 classes, any rescaling): the fused preorder
@@ -3666,7 +3569,7 @@ int dr_derivatives(plk_handle h, double* d1, double* d2) {
       if (f >= nt && (h->topo_kids[f].size() < 2 || h->topo_kids[f].size() > 3)) pre = false;
   h->dr_u_epoch = 0;
   if (pre) {
-    if ((rc = dr_fused_preorder(h, depth, parent, root, d1, d2))) return rc;
+    if ((rc = dr_fused_preorder(h, depth, root, d1, d2))) return rc;
     h->dr_u_epoch = h->state_epoch;  // (pi sits in the U of the root's sons)
     h->dr_u_pi = true;
     return PLK_OK;
@@ -3694,49 +3597,16 @@ int dr_derivatives(plk_handle h, double* d1, double* d2) {
       if (parent[v] >= 0 && parent[v] != root && h->topo_kids[parent[v]].size() == 2) fused[v] = 1;
   // U_v for every non-root node, one launch per (depth, child chunk)
   std::vector<KOp> flat;
-  std::vector<std::pair<size_t, int> > launches;
+  std::vector<OpLaunch> launches;
   for (size_t d = 1; d < depth.size(); ++d) {
-    std::vector<std::vector<KOp> > chunks;
-    for (int v : depth[d]) {
-      if (fused[v]) continue;
-      const int f = parent[v];
-      std::vector<int> ck_tip, ck_child, ck_branch;
-      if (f != root) {
-        ck_tip.push_back(0);
-        ck_child.push_back(h->dr_slot0 + f);
-        ck_branch.push_back(mat_base + f);
-      }
-      for (int s : h->topo_kids[f])
-        if (s != v) {
-          ck_tip.push_back(s < nt);
-          ck_child.push_back(s < nt ? s : s - nt);
-          ck_branch.push_back(s);
-        }
-      for (size_t k0 = 0, j = 0; k0 < ck_tip.size(); k0 += 3, ++j) {
-        KOp op;
-        std::memset(&op, 0, sizeof(op));
-        op.parent = h->dr_slot0 + v;
-        op.flags = k0 == 0 ? 0 : PLK_OP_ACCUMULATE;
-        for (size_t k = k0; k < ck_tip.size() && k < k0 + 3; ++k) {
-          const int i = op.n++;
-          op.is_tip[i] = ck_tip[k];
-          op.child[i] = ck_child[k];
-          op.branch[i] = ck_branch[k];
-        }
-        if (chunks.size() <= j) chunks.resize(j + 1);
-        chunks[j].push_back(op);
-      }
-    }
-    for (auto& ch : chunks) {
-      launches.push_back(std::make_pair(flat.size(), (int)ch.size()));
-      flat.insert(flat.end(), ch.begin(), ch.end());
-    }
+    std::vector<int> stored;
+    for (int v : depth[d])
+      if (!fused[v]) stored.push_back(v);
+    upper_ops(t, stored, nt, h->dr_slot0, mat_base, flat, launches);
   }
-  if ((rc = ensure_cap(h, (void**)&h->d_ops, &h->d_ops_cap, flat.size() * sizeof(KOp)))) return rc;
-  HIPCHK(h, hipMemcpyAsync(h->d_ops, flat.data(), flat.size() * sizeof(KOp), hipMemcpyHostToDevice, h->stream));
-  h->last_ops.clear();  // d_ops now holds the preorder ops
-  for (auto& l : launches)
-    if ((rc = launch_partials_ops(h, h->d_ops + l.first, l.second))) return rc;
+  if ((rc = upload_ops(h, flat, false))) return rc;
+  for (const OpLaunch& l : launches)
+    if ((rc = launch_partials_ops(h, h->d_ops + l.first, l.count))) return rc;
   // all branches in one reduction launch
   std::vector<DrBranch> br;
   for (size_t d = 1; d < depth.size(); ++d)
@@ -3766,25 +3636,7 @@ int dr_derivatives(plk_handle h, double* d1, double* d2) {
   if (!h->dr_out && (rc = dalloc(h, (void**)&h->dr_out, 2 * (size_t)nn * sizeof(double)))) return rc;
   HIPCHK(h, hipMemcpyAsync(h->d_drb, br.data(), br.size() * sizeof(DrBranch), hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipMemsetAsync(h->dr_out, 0, 2 * (size_t)nn * sizeof(double), h->stream));
-  DrArgs a;
-  a.partials = h->partials;
-  a.codes = h->codes;
-  a.code_table = h->code_table;
-  a.pmats = h->pmats;
-  a.dpmats = h->dpmats;
-  a.d2pmats = h->d2pmats;
-  a.pi = h->pi;
-  a.probs = h->probs;
-  a.weights = h->weights;
-  a.tipP = h->tipP;
-  a.n_codes = h->n_codes;
-  a.blk1 = h->dr_blk;
-  a.blk2 = h->dr_blk + br.size() * n_blk;
-  a.slot_stride = h->slot_stride;
-  a.n_pad = h->n_pad;
-  a.n_patterns = h->n_patterns;
-  a.C = C;
-  a.n_blk = n_blk;
+  DrArgs a = dr_args(h, br.size(), n_blk);
   a.G = 3 * (size_t)C * S * S * sizeof(double) <= 96 * 1024 ? C : 1;
   dim3 grid((unsigned)n_blk, (unsigned)br.size());
   const size_t lds = 3 * (size_t)a.G * S * S * sizeof(double);
@@ -3840,21 +3692,10 @@ int node_posteriors_local(plk_handle h, int n_nodes, const int32_t* nodes, doubl
   for (int i = 0; i < n_nodes; ++i)
     if (nodes[i] < nt || nodes[i] >= nn) return fail(h, PLK_ERR_ARG, "node %d is not an internal node", nodes[i]);
   if (h->trav_ops.empty()) return fail(h, PLK_ERR_STATE, "no traversal yet (plk_update_partials)");
-  std::vector<int> parent(nn, -1);
-  for (int n = 0; n < nn; ++n)
-    for (int c : h->topo_kids[n]) parent[c] = n;
-  int root = h->trav_ops.back().parent;
-  while (parent[root] >= 0) root = parent[root];
-  std::vector<char> in_tree(nn, 0);
-  {
-    std::vector<int> st(1, root);
-    while (!st.empty()) {
-      const int n = st.back();
-      st.pop_back();
-      in_tree[n] = 1;
-      for (int c : h->topo_kids[n]) st.push_back(c);
-    }
-  }
+  const TopoView t(h->topo_kids, h->trav_ops.back().parent);
+  const std::vector<int>& parent = t.parent;
+  const int root = t.root;
+  const std::vector<char> in_tree = t.in_tree();
   bool root_only = true;
   for (int i = 0; i < n_nodes; ++i) {
     if (!in_tree[nodes[i]]) return fail(h, PLK_ERR_ARG, "node %d is not in the current tree", nodes[i]);
@@ -3991,14 +3832,7 @@ int node_posteriors_local(plk_handle h, int n_nodes, const int32_t* nodes, doubl
   }
   if (restore) {
     const std::vector<plk_op> ops = h->trav_ops;
-    const int n_ops = (int)ops.size();
-    if (h->flags & PLK_FLAG_SUBTREE_PATTERNS)
-      rc = update_compressed(h, ops.data(), n_ops);
-    else if (tree4_supported(h) && fusable(ops.data(), n_ops))
-      rc = update_tree4(h, ops.data(), n_ops);
-    else
-      rc = update_levelwise(h, ops.data(), n_ops);
-    if (rc) return rc;
+    if ((rc = update_any(h, ops.data(), (int)ops.size()))) return rc;
   }
   return PLK_OK;
 }
@@ -4061,8 +3895,9 @@ int map_form_G(plk_handle h, int model) {
 // included.  pi is left out at the root's sons (the map kernels multiply it in); below them
 // M_f carries it exactly when U_f leaves it out, the rule of the levelwise preorder, so the
 // matrices written here are the ones that pass writes.  A tip is filled once per state_epoch.
-int map_fill_tip_uppers(plk_handle h, const std::vector<int>& tips, const std::vector<int>& parent, int root) {
-  const int nt = h->n_tips, nn = h->n_nodes, S = h->S, C = h->C;
+int map_fill_tip_uppers(plk_handle h, const std::vector<int>& tips, const TopoView& t) {
+  const int nt = h->n_tips, nn = h->n_nodes, S = h->S, C = h->C, root = t.root;
+  const std::vector<int>& parent = t.parent;
   if (h->tipu_epoch.empty()) h->tipu_epoch.assign(nt, 0);
   std::vector<int> todo;
   for (int v : tips)
@@ -4089,48 +3924,13 @@ int map_fill_tip_uppers(plk_handle h, const std::vector<int>& tips, const std::v
     HIPCHK(h, hipStreamSynchronize(h->stream));  // mlist is read by the copy
   }
   // ops of at most three children; the rest of a larger father accumulates in later launches
-  std::vector<std::vector<KOp> > chunks;
-  for (int v : todo) {
-    const int f = parent[v];
-    std::vector<int> ck_tip, ck_child, ck_branch;
-    if (f != root) {
-      ck_tip.push_back(0);
-      ck_child.push_back(h->dr_slot0 + f);
-      ck_branch.push_back(mat_base + f);
-    }
-    for (int s : h->topo_kids[f])
-      if (s != v) {
-        ck_tip.push_back(s < nt);
-        ck_child.push_back(s < nt ? s : s - nt);
-        ck_branch.push_back(s);
-      }
-    for (size_t k0 = 0, j = 0; k0 < ck_tip.size(); k0 += 3, ++j) {
-      KOp op;
-      std::memset(&op, 0, sizeof(op));
-      op.parent = h->dr_slot0 + v;
-      op.flags = k0 == 0 ? 0 : PLK_OP_ACCUMULATE;
-      for (size_t k = k0; k < ck_tip.size() && k < k0 + 3; ++k) {
-        const int i = op.n++;
-        op.is_tip[i] = ck_tip[k];
-        op.child[i] = ck_child[k];
-        op.branch[i] = ck_branch[k];
-      }
-      if (chunks.size() <= j) chunks.resize(j + 1);
-      chunks[j].push_back(op);
-    }
-  }
   std::vector<KOp> flat;
-  std::vector<std::pair<size_t, int> > launches;
-  for (auto& ch : chunks) {
-    launches.push_back(std::make_pair(flat.size(), (int)ch.size()));
-    flat.insert(flat.end(), ch.begin(), ch.end());
-  }
-  if ((rc = ensure_cap(h, (void**)&h->d_ops, &h->d_ops_cap, flat.size() * sizeof(KOp)))) return rc;
-  HIPCHK(h, hipMemcpyAsync(h->d_ops, flat.data(), flat.size() * sizeof(KOp), hipMemcpyHostToDevice, h->stream));
-  h->last_ops.clear();  // d_ops now holds these ops
-  for (auto& l : launches) {
+  std::vector<OpLaunch> launches;
+  upper_ops(t, todo, nt, h->dr_slot0, mat_base, flat, launches);
+  if ((rc = upload_ops(h, flat, false))) return rc;
+  for (const OpLaunch& l : launches) {
     TimedSpan span(h, PLK_TIME_PARTIALS, 0);
-    if ((rc = launch_partials_ops(h, h->d_ops + l.first, l.second))) return rc;
+    if ((rc = launch_partials_ops(h, h->d_ops + l.first, l.count))) return rc;
     if (span.stop()) h->n_launches++;
   }
   HIPCHK(h, hipStreamSynchronize(h->stream));  // flat is read by the copy
@@ -4152,21 +3952,10 @@ int branch_counts_local(plk_handle h, int n_branches, const int32_t* branches, d
   if (!(h->flags & PLK_FLAG_DOUBLE_RECURSIVE))
     return fail(h, PLK_ERR_STATE, "handle was not created with PLK_FLAG_DOUBLE_RECURSIVE");
   if (h->trav_ops.empty()) return fail(h, PLK_ERR_STATE, "no traversal yet (plk_update_partials)");
-  std::vector<int> parent(nn, -1);
-  for (int n = 0; n < nn; ++n)
-    for (int c : h->topo_kids[n]) parent[c] = n;
-  int root = h->trav_ops.back().parent;
-  while (parent[root] >= 0) root = parent[root];
-  std::vector<char> in_tree(nn, 0);
-  {
-    std::vector<int> st(1, root);
-    while (!st.empty()) {
-      const int n = st.back();
-      st.pop_back();
-      in_tree[n] = 1;
-      for (int c : h->topo_kids[n]) st.push_back(c);
-    }
-  }
+  const TopoView t(h->topo_kids, h->trav_ops.back().parent);
+  const std::vector<int>& parent = t.parent;
+  const int root = t.root;
+  const std::vector<char> in_tree = t.in_tree();
   for (int i = 0; i < n_branches; ++i) {
     if (branches[i] == root) return fail(h, PLK_ERR_ARG, "node %d is the root (it has no branch)", root);
     if (!in_tree[branches[i]]) return fail(h, PLK_ERR_ARG, "node %d is not in the current tree", branches[i]);
@@ -4183,7 +3972,7 @@ int branch_counts_local(plk_handle h, int n_branches, const int32_t* branches, d
   std::vector<int> tips;
   for (int i = 0; i < n_branches; ++i)
     if (branches[i] < nt) tips.push_back(branches[i]);
-  if ((rc = map_fill_tip_uppers(h, tips, parent, root))) return rc;
+  if ((rc = map_fill_tip_uppers(h, tips, t))) return rc;
   const bool mfma = S == 20 || S == 64;
   const int sub = mfma ? 64 : kMapThreads;                 // patterns per workgroup sum
   const int n_blk = (int)(h->n_pad / sub), per = kRootBlock / sub;
@@ -4310,21 +4099,10 @@ int nni_plan(plk_handle h, int n_moves, const int32_t* son, const int32_t* uncle
   if (h->trav_ops.empty()) return fail(h, PLK_ERR_STATE, "no traversal yet (plk_update_partials)");
   if (!(S == 2 || S == 3 || S == 4 || S == 20 || S == 64))
     return fail(h, PLK_ERR_UNSUPPORTED, "state count %d has no kernel instance", S);
-  std::vector<int> parent(nn, -1);
-  for (int n = 0; n < nn; ++n)
-    for (int c : h->topo_kids[n]) parent[c] = n;
-  int root = h->trav_ops.back().parent;
-  while (parent[root] >= 0) root = parent[root];
-  std::vector<char> in_tree(nn, 0);
-  {
-    std::vector<int> st(1, root);
-    while (!st.empty()) {
-      const int n = st.back();
-      st.pop_back();
-      in_tree[n] = 1;
-      for (int c : h->topo_kids[n]) st.push_back(c);
-    }
-  }
+  const TopoView t(h->topo_kids, h->trav_ops.back().parent);
+  const std::vector<int>& parent = t.parent;
+  const int root = t.root;
+  const std::vector<char> in_tree = t.in_tree();
   auto kid = [&](int v) {
     NniKid k;
     k.kind = v < 0 ? 2 : v < nt ? 1 : 0;
@@ -4791,9 +4569,7 @@ int plk_update_partials(plk_handle h, const plk_op* ops, int n_ops) {
       k.insert(k.end(), ops[i].child, ops[i].child + ops[i].n_children);
     }
   }
-  if (h->flags & PLK_FLAG_SUBTREE_PATTERNS) return update_compressed(h, ops, n_ops);
-  if (tree4_supported(h) && fusable(ops, n_ops)) return update_tree4(h, ops, n_ops);
-  return update_levelwise(h, ops, n_ops);
+  return update_any(h, ops, n_ops);
 }
 
 int plk_get_partials(plk_handle h, int node, double* out) {
@@ -5340,7 +5116,8 @@ static int branch_derivatives_local(plk_handle h, int branch, double* d1, double
 
 int plk_branch_derivatives(plk_handle h, int branch, double* d1, double* d2) {
   env_refresh();
-  if (h && !h->shards.empty()) return multi_branch_derivatives(h, branch, d1, d2);
+  if (h && !h->shards.empty())
+    return multi_sum_pair(h, [&](plk_handle x, double* u, double* v) { return plk_branch_derivatives(x, branch, u, v); }, d1, d2);
   if (!h) return fail(h, PLK_ERR_ARG, "null handle");
   double v[2] = {0.0, 0.0};
   int rc = branch_derivatives_local(h, branch, &v[0], &v[1]);
@@ -5361,33 +5138,17 @@ static int branch_derivatives_local(plk_handle h, int branch, double* d1, double
   if (!h->pi_set || !h->rates_set) return fail(h, PLK_ERR_STATE, "root frequencies / category rates not set");
   hipSetDevice(h->device);
   const int nt = h->n_tips;
-  // tree of the last traversal: sons per node (ops merged), parent map
-  std::vector<std::vector<int> > kids(h->n_nodes);
-  std::vector<int> parent(h->n_nodes, -1);
-  // the merged tree of every traversal so far (an incremental call lists only the
-  // ancestors of the changed branches)
-  for (int n = 0; n < h->n_nodes; ++n)
-    for (int c : h->topo_kids[n]) {
-      kids[n].push_back(c);
-      parent[c] = n;
-    }
+  const TopoView t(h->topo_kids, branch);
+  const std::vector<int>& parent = t.parent;
   if (parent[branch] < 0) return fail(h, PLK_ERR_ARG, "branch %d is not below any node of the last traversal", branch);
-  // every partial read along the path must be in HBM at full length: re-materialise if
-  // needed (a compressed traversal's slots hold distinct subtree patterns: the derivative
-  // re-runs the traversal uncompressed once, until the next compressed traversal)
-  bool need = (h->flags & PLK_FLAG_SUBTREE_PATTERNS) && !h->slots_expanded;
-  for (int n = parent[branch]; n >= 0; n = parent[n])
-    for (int c : kids[n])
-      if (c >= nt && !h->materialized[c - nt]) need = true;
-  if (need) {
-    int rc = materialize_last_traversal(h);
-    if (rc) return rc;
-  }
+  // every partial read along the path must be in HBM at full length
+  int rc = ensure_partials(h, t.path_sons(branch));
+  if (rc) return rc;
   // path program: father of the branch first, then every ancestor up to the root
   std::vector<DInstr> prog;
   int path = branch;
   for (int n = parent[branch]; n >= 0; path = n, n = parent[n]) {
-    for (int c : kids[n]) {
+    for (int c : t.kids[n]) {
       if (c == path) {
         if (path == branch)
           prog.push_back({D_PATH, c < nt ? 1 : 0, c < nt ? c : c - nt, c});
@@ -5402,14 +5163,10 @@ static int branch_derivatives_local(plk_handle h, int branch, double* d1, double
     prog.push_back({D_STEP, 0, 0, 0});
   }
   prog.push_back({D_END, 0, 0, 0});
-  int rc = ensure_cap(h, (void**)&h->d_dprog, &h->d_dprog_cap, prog.size() * sizeof(DInstr));
-  if (rc) return rc;
+  if ((rc = ensure_cap(h, (void**)&h->d_dprog, &h->d_dprog_cap, prog.size() * sizeof(DInstr)))) return rc;
   HIPCHK(h, hipMemcpyAsync(h->d_dprog, prog.data(), prog.size() * sizeof(DInstr), hipMemcpyHostToDevice,
                            h->stream));
-  if (!h->d1_sums) {
-    if ((rc = dalloc(h, (void**)&h->d1_sums, (size_t)(h->n_pad / 64) * sizeof(double)))) return rc;
-    if ((rc = dalloc(h, (void**)&h->d2_sums, (size_t)(h->n_pad / 64) * sizeof(double)))) return rc;
-  }
+  if ((rc = ensure_wave_sums(h))) return rc;
   DerivArgs a;
   a.partials = h->partials;
   a.codes = h->codes;
@@ -5431,37 +5188,14 @@ static int branch_derivatives_local(plk_handle h, int branch, double* d1, double
     case 4: deriv_kernel<4, 4><<<grid, 256, 0, h->stream>>>(a, h->d_dprog, h->pmats, h->dpmats, h->d2pmats, guard); break;
   }
   HIPCHK(h, hipGetLastError());
-  // fixed-order host sum of the wave sums (same order for any run)
-  const int n_waves = (int)((h->n_patterns + 63) / 64);
-  std::vector<double> w1(n_waves), w2(n_waves);
-  HIPCHK(h, hipMemcpyAsync(w1.data(), h->d1_sums, n_waves * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(w2.data(), h->d2_sums, n_waves * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  double s1 = 0.0, s2 = 0.0;
-  for (int i = 0; i < n_waves; ++i) {
-    s1 += w1[i];
-    s2 += w2[i];
-  }
-  if (d1) *d1 = s1;
-  if (d2) *d2 = s2;
-  return PLK_OK;
+  return read_wave_sums(h, d1, d2);
 }
 
 int plk_root_pair_derivatives(plk_handle h, int a, int b, double alpha, double beta, double* d1, double* d2) {
   env_refresh();
-  if (h && !h->shards.empty()) {
-    std::vector<double> u(h->shards.size()), v(h->shards.size());
-    const int rc = multi_run(h, [&](size_t i) { return plk_root_pair_derivatives(h->shards[i], a, b, alpha, beta, &u[i], &v[i]); });
-    if (rc) return rc;
-    double s1 = 0.0, s2 = 0.0;
-    for (size_t i = 0; i < u.size(); ++i) {  // shard order
-      s1 += u[i];
-      s2 += v[i];
-    }
-    if (d1) *d1 = s1;
-    if (d2) *d2 = s2;
-    return PLK_OK;
-  }
+  if (h && !h->shards.empty())
+    return multi_sum_pair(
+        h, [&](plk_handle x, double* u, double* v) { return plk_root_pair_derivatives(x, a, b, alpha, beta, u, v); }, d1, d2);
   if (!h) return fail(h, PLK_ERR_ARG, "null handle");
   double v[2] = {0.0, 0.0};
   int rc = root_pair_derivatives(h, a, b, alpha, beta, &v[0], &v[1]);

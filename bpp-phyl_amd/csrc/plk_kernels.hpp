@@ -20,6 +20,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "plk_topo.hpp"
+
 namespace plk {
 
 constexpr int kTile = 128;          // patterns per tile (layout granule)
@@ -29,23 +31,7 @@ constexpr double kScaleUp = 1157920892373161954235709850086879078532699846656405
 constexpr double kScaleThr = 1.0 / kScaleUp;                                                                 // 2^-256
 constexpr double kLn2x256 = 177.44567822334599921;                                                           // 256 ln 2
 
-// Device-side description of one partial update (children already resolved
-// into tip indices or internal slots).
-struct KOp {
-  int32_t parent;    // internal slot
-  int32_t n;         // number of children (1..3)
-  int32_t child[3];  // tip index (is_tip) or internal slot
-  int32_t branch[3]; // node index of the child = transition-matrix index
-  int32_t is_tip[3];
-  int32_t flags;     // PLK_OP_ACCUMULATE | kOpSigned
-};
-// Internal op flag: the vector being formed may have either sign (dP / d2P substituted on a
-// branch: the path and root-pair derivative vectors), so the rescale decision takes the largest
-// magnitude.  By the largest value a vector whose entries are all negative is never rescaled --
-// and a path vector stays all negative from there to the root (P and the siblings' products are
-// positive) until it leaves the double range.  Likelihood vectors keep the largest value: the
-// decision the oracle restates.
-constexpr int kOpSigned = 2;
+// KOp, the device-side description of one partial update, and kOpSigned: plk_topo.hpp
 __device__ __forceinline__ double scale_key(double v, bool sg) { return sg ? fabs(v) : v; }
 
 struct PartialsArgs {
