@@ -18,6 +18,7 @@
 #include "plk_nni.hpp"
 #include "plk_rell.hpp"
 #include "plk_pair.hpp"
+#include "plk_pars.hpp"
 #include "plk_exchange.hpp"
 
 #include <hip/hip_runtime.h>
@@ -30,6 +31,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <functional>
 #include <map>
@@ -427,6 +429,25 @@ struct plk_handle_s {
   char* d_pair = nullptr;
   size_t d_pair_cap = 0;
   int64_t pair_passes = 0;              // evaluation passes of the slowest pair, last plk_pair_distances
+  // Fitch parsimony (plk_pars.hpp): its own tree and arrays, nothing shared with the likelihood
+  bool weights_integral = true;         // every pattern weight is a non-negative integer below 2^32
+  int pars_S = 0;                       // parsimony states of plk_pars_set_code_masks (0: the code table's)
+  std::vector<uint64_t> pars_masks;     // its masks, caller's code numbering (empty: from the code table)
+  std::vector<uint64_t> pars_cmask;     // masks by compact code, as the last plk_pars_update uploaded them
+  int pars_width = 0;                   // bytes per stored set of that update: 1, 4 or 8
+  void* pars_sets = nullptr;            // [2 n_internal][n_pad] sets
+  size_t pars_sets_cap = 0;
+  uint16_t* pars_scores = nullptr;      // [2 n_internal][n_pad] scores
+  size_t pars_scores_cap = 0;
+  char* d_pars = nullptr;               // masks [256], total, the op program
+  size_t d_pars_cap = 0;
+  char* d_pars_moves = nullptr;         // a call's sums, then its moves
+  size_t d_pars_moves_cap = 0;
+  std::vector<std::vector<int> > pars_kids;  // sons per node of the last plk_pars_update tree, in op order
+  std::vector<int> pars_parent;         // father per node (-1: the root, or outside the tree)
+  int pars_root = -1;                   // -1: no plk_pars_update yet
+  uint64_t pars_total = 0;              // its weighted score
+  int64_t pars_launches = 0;            // kernel launches of the last parsimony call
   // RELL resampling (plk_rell.hpp): site rows [rell_n_rows][n_pad] and replicate weights
   // [rell_R][n_pad], padding 0.0; a multi-device parent keeps the two counts only
   double* rell_rows = nullptr;
@@ -1240,7 +1261,8 @@ int plk_destroy(plk_handle h) {
                   h->d_cherry_tips, h->d_cherry, h->d_drb, h->d_drm, h->dr_blk, h->dr_out, h->d_drpre, h->d_sbctr,
                   h->d_cherry_rows, h->d_kidsl, h->d_cls, h->d_ucodes_dc, h->d_units_start, h->d_post, h->post_buf,
                   h->count_G, h->wmats, h->d_mapb, h->map_blk, h->d_mapreq, h->d_nni, h->nni_vit, h->d_pair,
-                  h->rell_rows, h->rell_W, h->rell_stage, h->rell_bad};
+                  h->rell_rows, h->rell_W, h->rell_stage, h->rell_bad, h->pars_sets, h->pars_scores, h->d_pars,
+                  h->d_pars_moves};
   for (void* p : bufs)
     if (p) hipFree(p);
   if (h->h_req) (void)hipHostFree(h->h_req);
@@ -1371,6 +1393,7 @@ int plk_set_code_table(plk_handle h, int n_codes, const double* code_to_vec) {
   h->code_map.resize(256, -1);
   h->table_set = true;
   h->state_epoch++;
+  h->pars_root = -1;  // default masks come from the table
   return upload_compact_table(h);
 }
 
@@ -1410,6 +1433,7 @@ int plk_set_tip_codes(plk_handle h, int tip, const uint8_t* codes) {
   HIPCHK(h, hipMemcpy(h->codes + (size_t)tip * h->n_pad, cc.data(), (size_t)h->n_patterns, hipMemcpyHostToDevice));
   h->tip_set[tip] = 1;
   h->state_epoch++;
+  h->pars_root = -1;  // the parsimony pairs were formed from other codes
   h->ucodes_valid = false;
   h->cherry_codes_valid = false;
   return PLK_OK;
@@ -1422,6 +1446,10 @@ int plk_set_pattern_weights(plk_handle h, const double* weights) {
   hipSetDevice(h->device);
   HIPCHK(h, hipStreamSynchronize(h->stream));
   HIPCHK(h, hipMemcpy(h->weights, weights, (size_t)h->n_patterns * sizeof(double), hipMemcpyHostToDevice));
+  h->pars_root = -1;           // the parsimony score was summed with other weights
+  h->weights_integral = true;  // (plk_pars_update sums integers)
+  for (int64_t i = 0; i < h->n_patterns && h->weights_integral; ++i)
+    h->weights_integral = weights[i] >= 0.0 && weights[i] < 4294967296.0 && weights[i] == std::floor(weights[i]);
   h->fused_lnl_valid = false;  // a cached fused root reduction used the old weights
   return PLK_OK;
 }
@@ -5815,6 +5843,299 @@ int plk_pair_distances(plk_handle h, int n_pairs, const int32_t* tip_a, const in
 int plk_pair_passes(plk_handle h, int64_t* passes) {
   if (!h || !passes) return fail(h, PLK_ERR_ARG, "null argument");
   *passes = h->pair_passes;
+  return PLK_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Fitch parsimony (plk_pars.hpp): DRTreeParsimonyScore's lower, upper and root pairs of a whole
+// tree in one launch, and every NNI move of a round in one more.
+// ---------------------------------------------------------------------------
+// byte offsets into d_pars
+constexpr size_t kParsOffTotal = 256 * sizeof(uint64_t), kParsOffProg = kParsOffTotal + 16;
+
+static int pars_common(plk_handle h, bool need_tree) {
+  if (!h) return fail(nullptr, PLK_ERR_ARG, "null handle");
+  if (!h->shards.empty()) return fail(h, PLK_ERR_UNSUPPORTED, "parsimony on a multi-device handle");
+  if (h->comm) return fail(h, PLK_ERR_UNSUPPORTED, "parsimony under a communicator");
+  if (h->flags & PLK_FLAG_SUBTREE_PATTERNS)
+    return fail(h, PLK_ERR_UNSUPPORTED, "parsimony reads full-length tip codes (no pattern compression)");
+  if (need_tree && h->pars_root < 0) return fail(h, PLK_ERR_STATE, "no plk_pars_update yet");
+  return PLK_OK;
+}
+
+static ParsBufs pars_bufs(plk_handle h) {
+  ParsBufs b;
+  b.codes = h->codes;
+  b.weights = h->weights;
+  b.sets = h->pars_sets;
+  b.scores = h->pars_scores;
+  b.n_pad = h->n_pad;
+  b.n_patterns = h->n_patterns;
+  return b;
+}
+
+// pattern blocks of a launch with kVec patterns per lane
+static int pars_blocks(plk_handle h, int vec) { return (int)((h->n_pad / vec + kParsThreads - 1) / kParsThreads); }
+
+int plk_pars_set_code_masks(plk_handle h, int n_states_pars, int n_codes, const uint64_t* masks) {
+  env_refresh();
+  int rc = pars_common(h, false);
+  if (rc) return rc;
+  if (n_states_pars > 64) return fail(h, PLK_ERR_UNSUPPORTED, "%d parsimony states: a set holds at most 64", n_states_pars);
+  if (n_states_pars < 1 || !masks || n_codes < 1 || n_codes > 256)
+    return fail(h, PLK_ERR_ARG, "bad mask table (%d states, %d codes)", n_states_pars, n_codes);
+  const uint64_t all = n_states_pars == 64 ? ~(uint64_t)0 : (((uint64_t)1 << n_states_pars) - 1);
+  for (int c = 0; c < n_codes; ++c)
+    if (masks[c] == 0 || (masks[c] & ~all))
+      return fail(h, PLK_ERR_ARG, "code %d: mask 0x%llx is empty or has bits at or above state %d", c,
+                  (unsigned long long)masks[c], n_states_pars);
+  h->pars_S = n_states_pars;
+  h->pars_masks.assign(masks, masks + n_codes);
+  h->pars_root = -1;  // the stored pairs were formed from other masks
+  return PLK_OK;
+}
+
+int plk_pars_update(plk_handle h, const plk_op* ops, int n_ops) {
+  env_refresh();
+  int rc = pars_common(h, false);
+  if (rc) return rc;
+  if (!ops || n_ops <= 0) return fail(h, PLK_ERR_ARG, "empty op list");
+  const int nt = h->n_tips, nn = h->n_nodes, ni = h->n_internal;
+  if (nn > 65535) return fail(h, PLK_ERR_UNSUPPORTED, "%d nodes: parsimony scores are stored in 16 bits", nn);
+  std::vector<std::vector<int> > kids((size_t)nn);
+  std::vector<int> parent((size_t)nn, -1), order;
+  std::vector<char> done((size_t)nn, 0);
+  for (int i = 0; i < n_ops; ++i) {
+    const plk_op& o = ops[i];
+    if (o.parent < nt || o.parent >= nn) return fail(h, PLK_ERR_ARG, "op %d: parent %d is not an internal node", i, o.parent);
+    if (o.n_children < 1 || o.n_children > 3) return fail(h, PLK_ERR_ARG, "op %d: %d children", i, o.n_children);
+    if (o.flags & PLK_OP_ACCUMULATE) {
+      if (!done[o.parent]) return fail(h, PLK_ERR_ARG, "op %d: accumulate into node %d that no earlier op formed", i, o.parent);
+    } else {
+      if (done[o.parent]) return fail(h, PLK_ERR_ARG, "op %d: node %d formed twice", i, o.parent);
+      order.push_back(o.parent);
+    }
+    for (int k = 0; k < o.n_children; ++k) {
+      const int c = o.child[k];
+      if (c < 0 || c >= nn || c == o.parent) return fail(h, PLK_ERR_ARG, "op %d: bad child %d", i, c);
+      if (c < nt && !h->tip_set[c]) return fail(h, PLK_ERR_STATE, "op %d: tip %d has no codes", i, c);
+      if (c >= nt && !done[c]) return fail(h, PLK_ERR_ARG, "op %d: node %d is formed by no earlier op (postorder)", i, c);
+      if (parent[c] >= 0) return fail(h, PLK_ERR_ARG, "op %d: node %d has two fathers", i, c);
+      parent[c] = o.parent;
+      kids[o.parent].push_back(c);
+    }
+    done[o.parent] = 1;
+  }
+  const int root = ops[n_ops - 1].parent;
+  if (parent[root] >= 0) return fail(h, PLK_ERR_ARG, "the last op's parent %d is not the root", root);
+  if (kids[root].size() < 2) return fail(h, PLK_ERR_ARG, "root %d has one son", root);
+  for (int v : order)
+    if (v != root && parent[v] < 0) return fail(h, PLK_ERR_ARG, "node %d does not hang below the root %d", v, root);
+  if (!h->weights_integral)
+    return fail(h, PLK_ERR_STATE, "parsimony needs pattern weights that are non-negative integers below 2^32");
+  if (!h->table_set) return fail(h, PLK_ERR_STATE, "no code table");
+
+  // masks by compact code
+  const int Sp = h->pars_masks.empty() ? h->S : h->pars_S;
+  std::vector<uint64_t> cm(256, 0);
+  for (size_t cc = 0; cc < h->code_orig.size(); ++cc) {
+    const int c = h->code_orig[cc];
+    if (h->pars_masks.empty()) {
+      for (int s = 0; s < h->S; ++s)
+        if (h->code_table_host[(size_t)c * h->S + s] != 0.0) cm[cc] |= (uint64_t)1 << s;
+    } else {
+      if (c >= (int)h->pars_masks.size())
+        return fail(h, PLK_ERR_STATE, "tip code %d has no mask (%zu codes in plk_pars_set_code_masks)", c, h->pars_masks.size());
+      cm[cc] = h->pars_masks[(size_t)c];
+    }
+  }
+  const int width = Sp <= 8 ? 1 : Sp <= 32 ? 4 : 8;
+
+  // the op program: lower ops in the caller's postorder, upper ops in preorder, the root's op
+  std::vector<int32_t> prog;
+  int n_prog = 0;
+  auto low_ref = [&](int v) { return v < nt ? pars_ref(kParsTip, v) : pars_ref(kParsArr, v - nt); };
+  auto emit = [&](int out, const std::vector<int32_t>& in) {
+    prog.push_back(out);
+    prog.push_back((int32_t)in.size());
+    prog.insert(prog.end(), in.begin(), in.end());
+    ++n_prog;
+  };
+  auto emit_low = [&](int v) {
+    std::vector<int32_t> in;
+    for (int c : kids[v]) in.push_back(low_ref(c));
+    emit(v - nt, in);
+  };
+  for (int v : order)
+    if (v != root) emit_low(v);
+  std::vector<int> st(1, root);
+  while (!st.empty()) {
+    const int v = st.back();
+    st.pop_back();
+    if (v < nt) continue;
+    if (v != root) {
+      const int f = parent[v];
+      std::vector<int32_t> in;
+      if (f != root) in.push_back(pars_ref(kParsArr, ni + f - nt));
+      for (int c : kids[f])
+        if (c != v) in.push_back(low_ref(c));
+      emit(ni + v - nt, in);
+    }
+    for (size_t k = kids[v].size(); k-- > 0;) st.push_back(kids[v][k]);
+  }
+  emit_low(root);
+
+  hipSetDevice(h->device);
+  h->pars_root = -1;
+  const size_t n_arr = (size_t)2 * ni * h->n_pad;
+  if ((rc = ensure_cap(h, &h->pars_sets, &h->pars_sets_cap, n_arr * width))) return rc;
+  if ((rc = ensure_cap(h, (void**)&h->pars_scores, &h->pars_scores_cap, n_arr * sizeof(uint16_t)))) return rc;
+  if ((rc = ensure_cap(h, (void**)&h->d_pars, &h->d_pars_cap, kParsOffProg + prog.size() * sizeof(int32_t)))) return rc;
+  HIPCHK(h, hipMemcpyAsync(h->d_pars, cm.data(), 256 * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemsetAsync(h->d_pars + kParsOffTotal, 0, 16, h->stream));
+  HIPCHK(h, hipMemcpyAsync(h->d_pars + kParsOffProg, prog.data(), prog.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+  const ParsBufs b = pars_bufs(h);
+  const uint64_t* d_masks = reinterpret_cast<const uint64_t*>(h->d_pars);
+  const int32_t* d_prog = reinterpret_cast<const int32_t*>(h->d_pars + kParsOffProg);
+  unsigned long long* d_total = reinterpret_cast<unsigned long long*>(h->d_pars + kParsOffTotal);
+  if (width == 1)
+    pars_update_kernel<ParsLane4><<<pars_blocks(h, 4), kParsThreads, 0, h->stream>>>(b, d_masks, d_prog, n_prog, d_total);
+  else if (width == 4)
+    pars_update_kernel<ParsLane1<uint32_t> ><<<pars_blocks(h, 1), kParsThreads, 0, h->stream>>>(b, d_masks, d_prog, n_prog, d_total);
+  else
+    pars_update_kernel<ParsLane1<uint64_t> ><<<pars_blocks(h, 1), kParsThreads, 0, h->stream>>>(b, d_masks, d_prog, n_prog, d_total);
+  HIPCHK(h, hipGetLastError());
+  h->pars_launches = 1;
+  unsigned long long total = 0;
+  HIPCHK(h, hipMemcpyAsync(&total, d_total, sizeof(total), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));  // the program and the masks are locals
+  h->pars_total = total;
+  h->pars_cmask.swap(cm);
+  h->pars_width = width;
+  h->pars_kids.swap(kids);
+  h->pars_parent.swap(parent);
+  h->pars_root = root;
+  return PLK_OK;
+}
+
+int plk_pars_score(plk_handle h, uint64_t* score, uint32_t* site_scores) {
+  env_refresh();
+  int rc = pars_common(h, true);
+  if (rc) return rc;
+  if (!score) return fail(h, PLK_ERR_ARG, "null score");
+  *score = h->pars_total;
+  if (site_scores) return plk_pars_get_edge(h, h->pars_root, 0, nullptr, site_scores);
+  return PLK_OK;
+}
+
+int plk_pars_get_edge(plk_handle h, int node, int upper, uint64_t* sets, uint32_t* scores) {
+  env_refresh();
+  int rc = pars_common(h, true);
+  if (rc) return rc;
+  const int nt = h->n_tips, ni = h->n_internal;
+  if (node < 0 || node >= h->n_nodes || (node != h->pars_root && h->pars_parent[(size_t)node] < 0))
+    return fail(h, PLK_ERR_ARG, "node %d is not in the parsimony tree", node);
+  if (upper && (node < nt || node == h->pars_root))
+    return fail(h, PLK_ERR_ARG, "node %d (a tip or the root) has no upper pair", node);
+  if (!sets && !scores) return fail(h, PLK_ERR_ARG, "both outputs null");
+  hipSetDevice(h->device);
+  const size_t np = (size_t)h->n_patterns;
+  if (node < nt) {
+    std::vector<uint8_t> cc(np);
+    HIPCHK(h, hipMemcpyAsync(cc.data(), h->codes + (size_t)node * h->n_pad, np, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (size_t i = 0; i < np; ++i) {
+      if (sets) sets[i] = h->pars_cmask[cc[i]];
+      if (scores) scores[i] = 0;
+    }
+    return PLK_OK;
+  }
+  const size_t off = ((size_t)(upper ? ni : 0) + (size_t)(node - nt)) * (size_t)h->n_pad;
+  const int w = h->pars_width;
+  std::vector<uint8_t> raw(sets ? np * w : 0);
+  std::vector<uint16_t> sc(scores ? np : 0);
+  if (sets)
+    HIPCHK(h, hipMemcpyAsync(raw.data(), static_cast<const uint8_t*>(h->pars_sets) + off * w, np * w, hipMemcpyDeviceToHost, h->stream));
+  if (scores)
+    HIPCHK(h, hipMemcpyAsync(sc.data(), h->pars_scores + off, np * sizeof(uint16_t), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  for (size_t i = 0; i < np; ++i) {
+    if (sets) {
+      uint64_t v = 0;
+      std::memcpy(&v, raw.data() + i * w, (size_t)w);  // little endian
+      sets[i] = v;
+    }
+    if (scores) scores[i] = sc[i];
+  }
+  return PLK_OK;
+}
+
+int plk_pars_nni_scores(plk_handle h, int n_moves, const int32_t* son, const int32_t* uncle, int64_t* delta) {
+  env_refresh();
+  int rc = pars_common(h, true);
+  if (rc) return rc;
+  if (n_moves <= 0 || !son || !uncle || !delta) return fail(h, PLK_ERR_ARG, "bad move list (%d moves)", n_moves);
+  const int nt = h->n_tips, nn = h->n_nodes, ni = h->n_internal, root = h->pars_root;
+  const std::vector<int>& parent = h->pars_parent;
+  auto low_ref = [&](int v) { return v < nt ? pars_ref(kParsTip, v) : pars_ref(kParsArr, v - nt); };
+  std::vector<ParsMove> recs((size_t)n_moves);
+  for (int i = 0; i < n_moves; ++i) {
+    const int s = son[i], u = uncle[i];
+    if (s < 0 || s >= nn || u < 0 || u >= nn) return fail(h, PLK_ERR_ARG, "move %d: node out of range (%d, %d)", i, s, u);
+    if ((s != root && parent[(size_t)s] < 0) || (u != root && parent[(size_t)u] < 0))
+      return fail(h, PLK_ERR_ARG, "move %d: (%d, %d) is not in the current tree", i, s, u);
+    if (s == root || parent[(size_t)s] == root)
+      return fail(h, PLK_ERR_ARG, "move %d: son %d is the root or a son of the root", i, s);
+    const int p = parent[(size_t)s], g = parent[(size_t)p];
+    if (u == p || u == root || parent[(size_t)u] != g) return fail(h, PLK_ERR_ARG, "move %d: %d is no uncle of %d", i, u, s);
+    const std::vector<int>&kp = h->pars_kids[(size_t)p], &kg = h->pars_kids[(size_t)g];
+    if (kg.size() > (size_t)kParsMaxIn || kp.size() + 1 > (size_t)kParsMaxIn)
+      return fail(h, PLK_ERR_UNSUPPORTED, "move %d: node %d (%zu sons) or %d (%zu sons) has too many sons", i, p, kp.size(), g,
+                  kg.size());
+    ParsMove& r = recs[(size_t)i];
+    std::memset(&r, 0, sizeof(r));
+    if (g != root) r.gf[r.n_gf++] = pars_ref(kParsArr, ni + g - nt);
+    for (int o : kg)
+      if (o != p && o != u) r.gf[r.n_gf++] = low_ref(o);
+    r.gf[r.n_gf++] = low_ref(s);
+    for (int o : kp)
+      if (o != s) r.pp[r.n_pp++] = low_ref(o);
+    r.pp[r.n_pp++] = low_ref(u);
+    r.pp[r.n_pp++] = pars_ref(kParsGf, 0);
+  }
+  hipSetDevice(h->device);
+  const size_t off_moves = ((size_t)n_moves * sizeof(uint64_t) + 15) & ~(size_t)15;
+  if ((rc = ensure_cap(h, (void**)&h->d_pars_moves, &h->d_pars_moves_cap, off_moves + recs.size() * sizeof(ParsMove)))) return rc;
+  unsigned long long* d_sums = reinterpret_cast<unsigned long long*>(h->d_pars_moves);
+  const ParsMove* d_moves = reinterpret_cast<const ParsMove*>(h->d_pars_moves + off_moves);
+  HIPCHK(h, hipMemsetAsync(d_sums, 0, (size_t)n_moves * sizeof(uint64_t), h->stream));
+  HIPCHK(h, hipMemcpyAsync(h->d_pars_moves + off_moves, recs.data(), recs.size() * sizeof(ParsMove), hipMemcpyHostToDevice, h->stream));
+  const ParsBufs b = pars_bufs(h);
+  const uint64_t* d_masks = reinterpret_cast<const uint64_t*>(h->d_pars);
+  const int w = h->pars_width, n_blk = pars_blocks(h, w == 1 ? 4 : 1);
+  const int chunk = std::max(1, std::min(n_moves, (int)(2147483647LL / n_blk)));  // grid.x of one launch
+  h->pars_launches = 0;
+  for (int m0 = 0; m0 < n_moves; m0 += chunk) {
+    const unsigned grid = (unsigned)std::min(chunk, n_moves - m0) * (unsigned)n_blk;
+    if (w == 1)
+      pars_nni_kernel<ParsLane4><<<grid, kParsThreads, 0, h->stream>>>(b, d_masks, d_moves + m0, n_blk, d_sums + m0);
+    else if (w == 4)
+      pars_nni_kernel<ParsLane1<uint32_t> ><<<grid, kParsThreads, 0, h->stream>>>(b, d_masks, d_moves + m0, n_blk, d_sums + m0);
+    else
+      pars_nni_kernel<ParsLane1<uint64_t> ><<<grid, kParsThreads, 0, h->stream>>>(b, d_masks, d_moves + m0, n_blk, d_sums + m0);
+    HIPCHK(h, hipGetLastError());
+    h->pars_launches++;
+  }
+  std::vector<unsigned long long> sums((size_t)n_moves);
+  HIPCHK(h, hipMemcpyAsync(sums.data(), d_sums, sums.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  for (int i = 0; i < n_moves; ++i) delta[i] = (int64_t)sums[(size_t)i] - (int64_t)h->pars_total;
+  return PLK_OK;
+}
+
+int plk_pars_launches(plk_handle h, int64_t* launches) {
+  if (!h || !launches) return fail(h, PLK_ERR_ARG, "null argument");
+  *launches = h->pars_launches;
   return PLK_OK;
 }
 

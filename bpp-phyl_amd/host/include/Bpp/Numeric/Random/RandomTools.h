@@ -8,6 +8,8 @@
 
 #include <cstdint>
 #include <random>
+#include <stdexcept>
+#include <vector>
 
 namespace bpp {
 
@@ -27,6 +29,18 @@ struct RandomTools {
   template <class T>
   static T giveIntRandomNumberBetweenZeroAndEntry(T entry) {
     return static_cast<T>(giveRandomNumberBetweenZeroAndEntry(static_cast<double>(entry)));
+  }
+  // one element of v, each equally likely; without replacement it is taken out of v
+  template <class T>
+  static T pickOne(std::vector<T>& v, bool replace = false) {
+    if (v.empty()) throw std::out_of_range("RandomTools::pickOne: empty vector");
+    const size_t pos = giveIntRandomNumberBetweenZeroAndEntry<size_t>(v.size());
+    const T x = v[pos];
+    if (!replace) {
+      v[pos] = v.back();
+      v.pop_back();
+    }
+    return x;
   }
 };
 

@@ -111,6 +111,24 @@ class ProteicAlphabet : public Alphabet {
   }
 };
 
+// Presence / absence characters: 0 and 1, ? = either, gap = -1.
+class BinaryAlphabet : public Alphabet {
+ public:
+  BinaryAlphabet() {
+    type_ = "Binary alphabet";
+    size_ = 2;
+    for (int i = 0; i < 2; i++) {
+      chars_.push_back(std::to_string(i));
+      lookup_[chars_.back()] = i;
+      alias_.push_back(std::vector<int>(1, i));
+    }
+    chars_.push_back("?");
+    lookup_["?"] = 2;
+    alias_.push_back(std::vector<int>{0, 1});
+    lookup_["-"] = -1;
+  }
+};
+
 class CodonAlphabet : public Alphabet {
   const NucleicAlphabet* nuc_;
 

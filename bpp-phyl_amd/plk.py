@@ -44,7 +44,8 @@ EXPORTS = [
     "plk_get_count_matrix", "plk_branch_counts", "plk_nni_scores", "plk_nni_passes", "plk_pair_counts",
     "plk_pair_distances", "plk_pair_passes", "plk_site_rows_reserve", "plk_site_row_set", "plk_site_row_get",
     "plk_site_row_from_root", "plk_nni_site_rows", "plk_set_replicate_weights", "plk_replicate_sums",
-    "plk_replicate_passes",
+    "plk_replicate_passes", "plk_pars_set_code_masks", "plk_pars_update", "plk_pars_score", "plk_pars_get_edge",
+    "plk_pars_nni_scores", "plk_pars_launches",
 ]
 
 
@@ -154,6 +155,12 @@ def load(path: str = LIB_PATH) -> ct.CDLL:
         "plk_set_replicate_weights": ([ct.c_void_p, ct.c_int, dp], ct.c_int),
         "plk_replicate_sums": ([ct.c_void_p, ct.c_int, ct.c_int, dp, dp], ct.c_int),
         "plk_replicate_passes": ([ct.c_void_p, P(ct.c_int64)], ct.c_int),
+        "plk_pars_set_code_masks": ([ct.c_void_p, ct.c_int, ct.c_int, P(ct.c_uint64)], ct.c_int),
+        "plk_pars_update": ([ct.c_void_p, P(plk_op), ct.c_int], ct.c_int),
+        "plk_pars_score": ([ct.c_void_p, P(ct.c_uint64), P(ct.c_uint32)], ct.c_int),
+        "plk_pars_get_edge": ([ct.c_void_p, ct.c_int, ct.c_int, P(ct.c_uint64), P(ct.c_uint32)], ct.c_int),
+        "plk_pars_nni_scores": ([ct.c_void_p, ct.c_int, ip, ip, P(ct.c_int64)], ct.c_int),
+        "plk_pars_launches": ([ct.c_void_p, P(ct.c_int64)], ct.c_int),
         "plk_kernel_path": ([ct.c_void_p], ct.c_char_p),
         "plk_compressed_work": ([ct.c_void_p, P(ct.c_int64)], ct.c_int),
         "plk_evaluate": ([ct.c_void_p, ct.c_int, ip, ip, dp, P(plk_op), ct.c_int, ct.c_int, dp, dp], ct.c_int),
@@ -694,6 +701,55 @@ class Engine:
     def replicate_passes(self) -> int:
         n = ct.c_int64(0)
         self._chk(self.lib.plk_replicate_passes(self.h, ct.byref(n)))
+        return n.value
+
+    # Fitch parsimony: integer pairs (set, score) per edge, a tree of their own
+
+    def pars_set_code_masks(self, n_states_pars: int, masks):
+        """plk_pars_set_code_masks: one bit mask over n_states_pars parsimony states per tip code."""
+        m = np.ascontiguousarray(masks, dtype=np.uint64).ravel()
+        self._chk(self.lib.plk_pars_set_code_masks(self.h, int(n_states_pars), len(m),
+                                                   m.ctypes.data_as(ct.POINTER(ct.c_uint64))))
+
+    def pars_update(self, ops: Sequence[Tuple[int, Sequence[int], int]]):
+        """plk_pars_update: lower pairs, upper pairs and the root of the tree `ops` (postorder, the
+        last op's parent the root) in one launch."""
+        arr = self._op_array(ops)
+        self._chk(self.lib.plk_pars_update(self.h, arr, len(arr)))
+
+    def pars_score(self, want_sites: bool = False):
+        """plk_pars_score: the weighted score; with want_sites also the per-pattern scores (uint32)."""
+        sc = ct.c_uint64(0)
+        sites = np.empty(self.P, dtype=np.uint32) if want_sites else None
+        self._chk(self.lib.plk_pars_score(self.h, ct.byref(sc),
+                                          sites.ctypes.data_as(ct.POINTER(ct.c_uint32)) if want_sites else None))
+        return (sc.value, sites) if want_sites else sc.value
+
+    def pars_get_edge(self, node: int, upper: bool = False):
+        """plk_pars_get_edge: (sets uint64 [pattern], scores uint32 [pattern]) of low(node) or up(node)."""
+        sets = np.empty(self.P, dtype=np.uint64)
+        scores = np.empty(self.P, dtype=np.uint32)
+        self._chk(self.lib.plk_pars_get_edge(self.h, int(node), int(bool(upper)),
+                                             sets.ctypes.data_as(ct.POINTER(ct.c_uint64)),
+                                             scores.ctypes.data_as(ct.POINTER(ct.c_uint32))))
+        return sets, scores
+
+    def pars_nni_scores(self, son, uncle) -> np.ndarray:
+        """plk_pars_nni_scores: per move (son, uncle) the score of the swapped tree minus the current
+        score (int64)."""
+        s = np.ascontiguousarray(son, dtype=np.int32).ravel()
+        u = np.ascontiguousarray(uncle, dtype=np.int32).ravel()
+        if len(u) != len(s):
+            raise ValueError("son and uncle must have one entry per move")
+        ip = ct.POINTER(ct.c_int32)
+        delta = np.empty(len(s), dtype=np.int64)
+        self._chk(self.lib.plk_pars_nni_scores(self.h, len(s), s.ctypes.data_as(ip), u.ctypes.data_as(ip),
+                                               delta.ctypes.data_as(ct.POINTER(ct.c_int64))))
+        return delta
+
+    def pars_launches(self) -> int:
+        n = ct.c_int64(0)
+        self._chk(self.lib.plk_pars_launches(self.h, ct.byref(n)))
         return n.value
 
     def set_timing(self, on: bool):

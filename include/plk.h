@@ -56,7 +56,8 @@ extern "C" {
 #endif
 
 /* 2: plk_timing gained `evaluations` and `host_us` (a caller built against 1 must not pass
- * its smaller struct to plk_get_timing_ex) */
+ * its smaller struct to plk_get_timing_ex).  Added entry points (the plk_pars_* calls last)
+ * change no struct or signature and leave the version as it is. */
 #define PLK_ABI_VERSION 2
 
 enum {
@@ -591,6 +592,67 @@ int plk_pair_distances(plk_handle h, int n_pairs, const int32_t* tip_a, const in
                        int32_t* status /* n_pairs, nullable */);
 /* Evaluation passes of the slowest pair of the last plk_pair_distances on this handle. */
 int plk_pair_passes(plk_handle h, int64_t* passes);
+
+/* Maximum parsimony (Fitch, unordered states): DRTreeParsimonyScore of the reference
+ * (Parsimony/DRTreeParsimonyScore.cpp, with DRTreeParsimonyData and AbstractTreeParsimonyScore),
+ * all in integers.  A set is a bit mask over S_p <= 64 parsimony states; a pair is (set, score).
+ * F(x_1, ..., x_k) is the reference's sequential fold (:276-311): start from x_1; for each further
+ * x_j add its score and intersect the sets; where the intersection is empty take the union and add
+ * 1.  The score of F does not depend on the order of its inputs, the set does, so the order below
+ * is part of the definition.  For the tree of an op list (sons in the ops' order; an
+ * PLK_OP_ACCUMULATE op appends its sons to the parent's):
+ *   low(tip) = (mask[code], 0),   low(v) = F(low(c_1), ..., low(c_k))             (:132-182)
+ *   up(v)    = F([up(f), unless f is the root], low(c) for every son c of f other than v, in
+ *              order) for every internal v other than the root, f its father      (:184-238)
+ *   score    = sum_p w_p low(root).score[p]                                       (:240-256)
+ * and for a move (son s, uncle u), p the father of s, g the father of p, u a son of g other than p
+ * (:314-383):
+ *   gf = F([up(g), unless g is the root], low(o) for o son of g, o not p, o not u, in order, low(s))
+ *   pp = F(low(o) for o son of p, o not s, in order, low(u), gf)
+ *   delta = sum_p w_p pp.score[p] - score,
+ * which is the score of the tree with s and u exchanged minus the current score wherever every
+ * internal node but the root has two sons (the root: two or three); the fold is not associative,
+ * so around an internal node of three sons delta is what the fold gives and no more.
+ *
+ * The parsimony calls keep a tree and arrays of their own (per internal node a lower and an upper
+ * array of sets -- 1, 4 or 8 bytes by S_p -- and of 16-bit scores): they change no partial, P(t),
+ * plk_kernel_path or later likelihood result of the handle, and need no model, rate or P(t).
+ * Deliberate limit: PLK_ERR_UNSUPPORTED on a multi-device handle, under a communicator and with
+ * PLK_FLAG_SUBTREE_PATTERNS -- the work is too light to need more than one device.
+ *
+ * plk_pars_set_code_masks: one mask per tip code of plk_set_code_table's numbering; n_states_pars
+ * may differ from the handle's state count (a gap as a state of its own: S + 1).  Never called:
+ * bit s of a code's mask is set where code_to_vec[code][s] != 0.  PLK_ERR_UNSUPPORTED for
+ * n_states_pars > 64; PLK_ERR_ARG for a zero mask, bits at or above n_states_pars, n_codes outside
+ * 1..256.  New masks, a new code table, new tip codes and new pattern weights drop the pairs of
+ * an earlier plk_pars_update: the calls that read them return PLK_ERR_STATE until the next one. */
+int plk_pars_set_code_masks(plk_handle h, int n_states_pars, int n_codes, const uint64_t* masks);
+/* Lower pairs, upper pairs and the root of the whole tree in one kernel launch (a lane keeps its
+ * patterns from the first op to the last).  Ops in postorder with at most 3 sons each, as for
+ * plk_update_partials, every internal son formed by an earlier op of the same call; the last op's
+ * parent is the root, which has at least two sons.  Weights are the pattern weights plk_root_loglik
+ * reads; each must be a non-negative integer below 2^32 (PLK_ERR_STATE otherwise), and sums are
+ * taken in uint64_t, so no result depends on the launch geometry.  PLK_ERR_STATE for a tip without
+ * codes or a tip code without a mask; PLK_ERR_UNSUPPORTED for a handle of more than 65535 nodes
+ * (the 16-bit scores).  Synchronises. */
+int plk_pars_update(plk_handle h, const plk_op* ops, int n_ops);
+/* The weighted score of the last plk_pars_update and (nullable) low(root).score per pattern. */
+int plk_pars_score(plk_handle h, uint64_t* score, uint32_t* site_scores /* n_patterns, or NULL */);
+/* low(node) (upper == 0; a tip is allowed) or up(node) of the last plk_pars_update; either output
+ * may be NULL (not both).  PLK_ERR_ARG for up of the root or of a tip and for a node outside the
+ * tree. */
+int plk_pars_get_edge(plk_handle h, int node, int upper, uint64_t* sets /* n_patterns, or NULL */,
+                      uint32_t* scores /* n_patterns, or NULL */);
+/* delta of every listed move of the last plk_pars_update tree, one workgroup per move and pattern
+ * block, one launch for all moves (DRTreeParsimonyScore::testNNI, :314-383, for every move of a
+ * round of NNITopologySearch at once).  PLK_ERR_ARG as plk_nni_scores: s the root or a son of the
+ * root, u not a son of g other than p, an index out of range or outside the tree, n_moves <= 0;
+ * PLK_ERR_UNSUPPORTED when g has more than 8 sons or p more than 7.  Synchronises. */
+int plk_pars_nni_scores(plk_handle h, int n_moves, const int32_t* son, const int32_t* uncle,
+                        int64_t* delta /* n_moves */);
+/* Kernel launches of the last plk_pars_update or plk_pars_nni_scores on this handle.
+ * Every parsimony call: PLK_ERR_STATE before plk_pars_update (where it reads its tree). */
+int plk_pars_launches(plk_handle h, int64_t* launches);
 
 /* Instrumentation: HIP-event timing on the handle's stream of the kernels selected
  * by the mask given to plk_set_timing (0 = off).  Each timed launch adds an event
