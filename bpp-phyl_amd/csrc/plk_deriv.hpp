@@ -12,7 +12,12 @@
 // path together in registers (nothing is written to HBM); siblings are read from the
 // materialised partials (or tip codes).  L is recomputed along the path from the same
 // inputs as dL, so dl / l is exact even with power-of-two rescaling (L, dL, d2L are
-// rescaled jointly by L's maximum).
+// rescaled jointly by L's maximum).  The rescale follows every son, not every node, and
+// repeats until L's maximum is back above 2^-256: a node multiplies all its sons in registers
+// (five at a polytomy, where the traversal's ACCUMULATE ops rescale after every three), each
+// anywhere in [2^-256, 1) or lower, and one factor 2^256 per node left l = dl = 0 and a NaN
+// for the branch.  Powers of two are exact and only dl / l and d2l / l leave the kernel, so
+// wherever nothing underflowed the results are bitwise what one rescale per node gave.
 #pragma once
 
 #include "plk_kernels.hpp"
@@ -93,16 +98,12 @@ __global__ __launch_bounds__(256) void deriv_kernel(DerivArgs a, const DInstr* _
     if (in.op == D_END) break;
     const size_t moff = (size_t)in.b * C * S * S;
     if (in.op == D_STEP) {
-      // node complete: joint rescale by L's maximum (keeps dl / l exact)
-      double m = 0.0;
-#pragma unroll
-      for (int i = 0; i < C * S; ++i) m = fmax(m, nL[i]);
-      const double f = (m > 0.0 && m < kScaleThr) ? kScaleUp : 1.0;
+      // node complete (the running product was rescaled after its last son)
 #pragma unroll
       for (int i = 0; i < C * S; ++i) {
-        L[i] = nL[i] * f;
-        dL[i] = ndL[i] * f;
-        d2L[i] = nd2L[i] * f;
+        L[i] = nL[i];
+        dL[i] = ndL[i];
+        d2L[i] = nd2L[i];
         nL[i] = ndL[i] = nd2L[i] = 1.0;
       }
       first = false;
@@ -139,6 +140,19 @@ __global__ __launch_bounds__(256) void deriv_kernel(DerivArgs a, const DInstr* _
         ndL[i] *= s[i];
         nd2L[i] *= s[i];
       }
+    }
+    // joint rescale by L's maximum (keeps dl / l exact), until it is back above 2^-256
+    double m = 0.0;
+#pragma unroll
+    for (int i = 0; i < C * S; ++i) m = fmax(m, nL[i]);
+    while (m > 0.0 && m < kScaleThr) {
+#pragma unroll
+      for (int i = 0; i < C * S; ++i) {
+        nL[i] *= kScaleUp;
+        ndL[i] *= kScaleUp;
+        nd2L[i] *= kScaleUp;
+      }
+      m *= kScaleUp;
     }
   }
   // root: l (with the reference's per-class guards), dl, d2l

@@ -386,6 +386,20 @@ typedef __attribute__((address_space(4))) const double* DrCPd;
 // states and classes (x 2^256 when that maximum is below 2^-256, the traversal's rule)
 // after the class loop, in place: the lane rewrites its own stores.  The branch terms need
 // no scale bookkeeping: l, l', l'' share U's and L's factors, and only their ratios enter.
+// They do need the product to stay a normal double: at a three-son node l multiplies U_f,
+// two siblings and the son's own L, four stored vectors of which each may sit near 2^-256
+// (lower after a three-son op of small sons), and l = l' = l'' = 0 gave NaN for the branch.
+// So with SCALE an exact power of two, 2^-e with e the exponent of the vector's joint maximum
+// over classes and states (dr_pow2_exp), is taken out of U_f and of every son's L as they are
+// loaded; l, l', l'' share it, and the stored U gets it back (ldexp: one rounding, and none
+// while the value is a normal double), so U and every ratio are bitwise what they were
+// wherever nothing underflowed.
+__device__ __forceinline__ int dr_pow2_exp(double m) {
+  if (!(m > 0.0 && m <= 1.79769313486231570815e308)) return 0;
+  const int e = ilogb(m);
+  return e < -1000 ? -1000 : e;
+}
+
 template <int C, bool SCALE = false>
 // (part / uout: the partial slots read (L, U_f) and written (U of internal sons) -- never
 // the same slot within a launch, so both are restrict and the next class's loads may be
@@ -435,15 +449,42 @@ __global__ __launch_bounds__(kDrThreads) void dr_pre_s4_kernel(const DrPreOp* __
   }
   const bool root = op.uf_slot < 0;
   const double* ub = part + (int64_t)(root ? 0 : op.uf_slot) * a.slot_stride + tb;
+  // SCALE: the exponents taken out of each son's L and of U_f, and what a stored U_i gets back
+  int eL[3] = {0, 0, 0}, eU = 0;
+  double sL[3] = {1.0, 1.0, 1.0}, sU = 1.0;
+  if (SCALE) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      if (j >= op.n) continue;
+      double m = 0.0;
+      for (int c = 0; c < (scs[j] ? C : 1); ++c)
+#pragma unroll
+        for (int z = 0; z < S; ++z) m = fmax(m, sb[j][c * scs[j] + z * sst[j]]);
+      eL[j] = dr_pow2_exp(m);
+      sL[j] = ldexp(1.0, -eL[j]);
+    }
+    if (!root) {
+      double m = 0.0;
+      for (int e = 0; e < C * S; ++e) m = fmax(m, ub[(int64_t)e * kTile]);
+      eU = dr_pow2_exp(m);
+      sU = ldexp(1.0, -eU);
+    }
+  }
   double Lb[2][3][S], Ub[2][S];
   auto load = [&](int c, int bf) {
 #pragma unroll
     for (int j = 0; j < 3; ++j)
 #pragma unroll
-      for (int z = 0; z < S; ++z) Lb[bf][j][z] = sb[j][c * scs[j] + z * sst[j]];
+      for (int z = 0; z < S; ++z) {
+        const double v = sb[j][c * scs[j] + z * sst[j]];
+        Lb[bf][j][z] = SCALE ? v * sL[j] : v;
+      }
     if (!root)
 #pragma unroll
-      for (int y = 0; y < S; ++y) Ub[bf][y] = ub[(int64_t)c * S * kTile + (int64_t)y * kTile];
+      for (int y = 0; y < S; ++y) {
+        const double v = ub[(int64_t)c * S * kTile + (int64_t)y * kTile];
+        Ub[bf][y] = SCALE ? v * sU : v;
+      }
   };
   load(0, 0);
 #pragma unroll
@@ -492,11 +533,21 @@ __global__ __launch_bounds__(kDrThreads) void dr_pre_s4_kernel(const DrPreOp* __
       }
       if (op.uslot[i] >= 0) {
         double* dst = uout + (int64_t)op.uslot[i] * a.slot_stride + co;
+        if (SCALE) {
+          int eb = eU;  // the stored U_i as it always was: the exponents of U_f and of the siblings go back in
 #pragma unroll
-        for (int x = 0; x < S; ++x) dst[(int64_t)x * kTile] = u[x];
-        if (SCALE)
+          for (int j = 0; j < 3; ++j)
+            if (j != i && j < op.n) eb += eL[j];
 #pragma unroll
-          for (int x = 0; x < S; ++x) umax[i] = fmax(umax[i], u[x]);
+          for (int x = 0; x < S; ++x) {
+            const double us = ldexp(u[x], eb);
+            dst[(int64_t)x * kTile] = us;
+            umax[i] = fmax(umax[i], us);
+          }
+        } else {
+#pragma unroll
+          for (int x = 0; x < S; ++x) dst[(int64_t)x * kTile] = u[x];
+        }
       }
       const DrCPd D1 = (DrCPd)(a.dpmats + ((int64_t)op.son[i] * C + c) * S * S);
       const DrCPd D2 = (DrCPd)(a.d2pmats + ((int64_t)op.son[i] * C + c) * S * S);
@@ -607,15 +658,42 @@ __global__ __launch_bounds__(256) void dr_pre_m20_kernel(const DrPreOp* __restri
       d[X] = acc;
     }
   };
+  // SCALE: an exact power of two out of every son's L and of U_f, as dr_pre_s4_kernel has it
+  // (the joint maximum of a pattern is spread over its four lanes)
+  int eL[3] = {0, 0, 0}, eU = 0;
+  double sL[3] = {1.0, 1.0, 1.0}, sU = 1.0;
+  if (SCALE) {
+    auto joint = [&](const double* base, int64_t cstride, int nc) {
+      double m = 0.0;
+      for (int c = 0; c < nc; ++c)
+#pragma unroll
+        for (int X = 0; X < XB; ++X) m = fmax(m, base[c * cstride + (int64_t)(4 * X) * (cstride ? kTile : 1)]);
+      m = fmax(m, __shfl_xor(m, 16, 64));
+      return fmax(m, __shfl_xor(m, 32, 64));
+    };
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      if (j >= nsn) continue;
+      const double m = op.is_tip[j]
+                           ? joint(a.code_table + (int64_t)a.codes[(int64_t)op.idx[j] * a.n_pad + p] * S + hi, 0, 1)
+                           : joint(a.partials + (int64_t)op.idx[j] * a.slot_stride + tb, (int64_t)S * kTile, C);
+      eL[j] = dr_pow2_exp(m);
+      sL[j] = ldexp(1.0, -eL[j]);
+    }
+    if (!root) {
+      eU = dr_pow2_exp(joint(a.partials + (int64_t)op.uf_slot * a.slot_stride + tb, (int64_t)S * kTile, C));
+      sU = ldexp(1.0, -eU);
+    }
+  }
   auto loadL = [&](int j, int c, double (&v)[XB]) {
     if (op.is_tip[j]) {
       const double* row = a.code_table + (int64_t)a.codes[(int64_t)op.idx[j] * a.n_pad + p] * S + hi;
 #pragma unroll
-      for (int X = 0; X < XB; ++X) v[X] = row[4 * X];
+      for (int X = 0; X < XB; ++X) v[X] = SCALE ? row[4 * X] * sL[j] : row[4 * X];
     } else {
       const double* L = a.partials + (int64_t)op.idx[j] * a.slot_stride + tb + (int64_t)c * S * kTile;
 #pragma unroll
-      for (int X = 0; X < XB; ++X) v[X] = L[(int64_t)(4 * X) * kTile];
+      for (int X = 0; X < XB; ++X) v[X] = SCALE ? L[(int64_t)(4 * X) * kTile] * sL[j] : L[(int64_t)(4 * X) * kTile];
     }
   };
   auto dot = [&](const double (&u)[XB], const double (&t)[XB]) {
@@ -663,7 +741,7 @@ __global__ __launch_bounds__(256) void dr_pre_m20_kernel(const DrPreOp* __restri
       const double* U = a.partials + (int64_t)op.uf_slot * a.slot_stride + tb + (int64_t)c * S * kTile;
       double uf[XB];
 #pragma unroll
-      for (int X = 0; X < XB; ++X) uf[X] = U[(int64_t)(4 * X) * kTile];
+      for (int X = 0; X < XB; ++X) uf[X] = SCALE ? U[(int64_t)(4 * X) * kTile] * sU : U[(int64_t)(4 * X) * kTile];
       matvec(mu, uf, 0, true);  // M_f U_f = P_f^T U_f
     }
     double Q[3][XB];
@@ -688,10 +766,15 @@ __global__ __launch_bounds__(256) void dr_pre_m20_kernel(const DrPreOp* __restri
       }
       if (op.uslot[i] >= 0) {
         double* dst = a.uout + (int64_t)op.uslot[i] * a.slot_stride + tb + (int64_t)c * S * kTile;
+        int eb = eU;  // SCALE: the stored U_i gets the exponents of U_f and of the siblings back
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+          if (j != i && j < nsn) eb += eL[j];
 #pragma unroll
         for (int X = 0; X < XB; ++X) {
-          dst[(int64_t)(4 * X) * kTile] = u[X];
-          if (SCALE) umax[i] = fmax(umax[i], u[X]);
+          const double us = SCALE ? ldexp(u[X], eb) : u[X];
+          dst[(int64_t)(4 * X) * kTile] = us;
+          if (SCALE) umax[i] = fmax(umax[i], us);
         }
       }
       const double s0 = dot(u, Q[i]);

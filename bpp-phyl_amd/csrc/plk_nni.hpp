@@ -19,6 +19,16 @@
 // gamma are built from the same stored vectors, so their power-of-two scale factors cancel and
 // the scale counts are never read (the rule of plk_dr.hpp, plk_post.hpp, plk_map.hpp).
 //
+// That holds while the product of the stored vectors is a normal double.  Under PLK_FLAG_SCALING
+// each stored vector has its joint maximum anywhere in [2^-256, 1) (lower after a three-son op
+// of small sons: one factor 2^256 per op), and l_cur multiplies four of them on a binary tree
+// (U_g, L_s, L_u, the other son of p) and six at trifurcations: the product reached 0 and the
+// pattern was dropped without a word (1 / l_cur = 0: it added 0 to every sum, and its site row
+// was 0.0).  So the build first takes an exact power of two out of each vector -- 2^-e, e the
+// exponent of its joint maximum over classes and states (nni_pow2) -- which puts every maximum
+// in [1, 2).  l_cur, gamma and d share the factor, 1 / l_cur carries its inverse, and powers of
+// two are exact: wherever nothing underflowed before, every result is bitwise what it was.
+//
 // nni_coef_* pay the matrix-vector products once per move and store the rows
 // [move][c S + k][n_pad] of gamma plus two rows: 1 / l_cur (0 where l_cur is not a positive
 // finite number) -- l_cur needs every class before any gamma can be divided, and the extra row
@@ -79,6 +89,13 @@ struct NniArgs {
 constexpr int kNniThreads = 256;
 constexpr int kNniExtra = 2;  // rows after gamma: 1 / l_cur, d
 
+// 2^-e for a joint maximum m in [2^e, 2^(e+1)); 1 for a vector of zeros (or anything not finite)
+__device__ __forceinline__ double nni_pow2(double m) {
+  if (!(m > 0.0 && m <= 1.79769313486231570815e308)) return 1.0;
+  const int e = ilogb(m);
+  return ldexp(1.0, e < -1000 ? 1000 : -e);
+}
+
 // S <= 4: one lane = one pattern, the move record and every matrix through the constant
 // address space (scalar loads, as map_s4_kernel).  CT > 0: the class count is a compile-time
 // constant and the class loop is unrolled, so the loads of all classes are in flight together.
@@ -93,6 +110,30 @@ __global__ __launch_bounds__(kNniThreads) void nni_coef_s4_kernel(const NniMove*
   const int64_t tb = (p >> 7) * CS * kTile + (p & (kTile - 1));
   const DrCPd V = (DrCPd)(a.V + (int64_t)model * S * S);
   const DrCPd Vi = (DrCPd)(a.Vinv + (int64_t)model * S * S);
+  // the power of two taken out of each vector: sc[j] for subtree j, sc[5] for U_g
+  double sc[6];
+#pragma unroll
+  for (int j = 0; j < 5; ++j) {
+    const int kind = w[3 * j], child = w[3 * j + 1];
+    double m = 0.0;
+    if (kind == 1) {
+      const double* __restrict__ row = a.code_table + (size_t)a.codes[(size_t)child * a.n_pad + p] * S;
+#pragma unroll
+      for (int y = 0; y < S; ++y) m = fmax(m, row[y]);
+    } else if (kind == 0) {
+      const double* __restrict__ Lb = a.partials + (int64_t)child * a.slot_stride + tb;
+      for (int e = 0; e < CS; ++e) m = fmax(m, Lb[(int64_t)e * kTile]);
+    }
+    sc[j] = nni_pow2(m);
+  }
+  {
+    double m = 0.0;
+    if (!g_root) {
+      const double* __restrict__ Ub = a.partials + (int64_t)g_uslot * a.slot_stride + tb;
+      for (int e = 0; e < CS; ++e) m = fmax(m, Ub[(int64_t)e * kTile]);
+    }
+    sc[5] = nni_pow2(m);
+  }
   // q = P_v L_v of subtree j for class c
   auto q = [&](int j, int c, double (&r)[S]) {
     const int kind = w[3 * j], child = w[3 * j + 1], node = w[3 * j + 2];
@@ -100,11 +141,11 @@ __global__ __launch_bounds__(kNniThreads) void nni_coef_s4_kernel(const NniMove*
     if (kind == 1) {
       const double* __restrict__ row = a.code_table + (size_t)a.codes[(size_t)child * a.n_pad + p] * S;
 #pragma unroll
-      for (int y = 0; y < S; ++y) L[y] = row[y];
+      for (int y = 0; y < S; ++y) L[y] = row[y] * sc[j];
     } else {
       const double* __restrict__ Lb = a.partials + (int64_t)child * a.slot_stride + tb;
 #pragma unroll
-      for (int y = 0; y < S; ++y) L[y] = Lb[((int64_t)c * S + y) * kTile];
+      for (int y = 0; y < S; ++y) L[y] = Lb[((int64_t)c * S + y) * kTile] * sc[j];
     }
     const DrCPd P = (DrCPd)(a.pmats + ((int64_t)node * C + c) * S * S);
 #pragma unroll
@@ -128,7 +169,7 @@ __global__ __launch_bounds__(kNniThreads) void nni_coef_s4_kernel(const NniMove*
       double u[S];
 #pragma unroll
       for (int y = 0; y < S; ++y) {
-        const double v = Ub[((int64_t)c * S + y) * kTile];
+        const double v = Ub[((int64_t)c * S + y) * kTile] * sc[5];
         u[y] = g_pi ? v * ((DrCPd)a.pi)[y] : v;
       }
 #pragma unroll
@@ -218,6 +259,27 @@ __global__ __launch_bounds__(kNniThreads) __attribute__((amdgpu_waves_per_eu(S =
   for (int64_t blk = blockIdx.x; blk < a.n_blk; blk += gridDim.x) {
     const int64_t p = blk * 64 + 16 * g + lc;
     const int64_t tb = (p >> 7) * CS * kTile + (p & (kTile - 1));
+    // the power of two taken out of each vector (see the head of this file): sc[j] for subtree
+    // j, sc[5] for U_g; the joint maximum of a pattern is spread over its four lanes
+    double sc[6];
+    for (int j = 0; j < 6; ++j) {
+      const int kind = j < 5 ? mv.k[j].kind : mv.g_root ? 2 : 0;
+      const double* row = a.code_table + (size_t)(kind == 1 ? a.codes[(size_t)mv.k[j].child * a.n_pad + p] : 0) * S;
+      const double* Lb = a.partials + (int64_t)(kind == 1 ? 0 : j < 5 ? mv.k[j].child : mv.g_uslot) * a.slot_stride + tb;
+      double m = 0.0;
+      if (kind != 2)
+        for (int c = 0; c < (kind == 1 ? 1 : C); ++c)
+#pragma unroll
+          for (int xt = 0; xt < XT; ++xt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int y = 16 * xt + lr + 4 * r;
+              if (m_valid<S>(xt, r, lr)) m = fmax(m, kind == 1 ? row[y] : Lb[(int64_t)(c * S + y) * kTile]);
+            }
+      m = fmax(m, __shfl_xor(m, 16, 64));
+      m = fmax(m, __shfl_xor(m, 32, 64));
+      sc[j] = nni_pow2(m);
+    }
     // q = P_v L_v of subtree j for class c
     auto q = [&](int j, int c, f64x4m (&d)[XT]) {
       const NniKid kd = mv.k[j];
@@ -229,7 +291,7 @@ __global__ __launch_bounds__(kNniThreads) __attribute__((amdgpu_waves_per_eu(S =
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int y = 16 * xt + lr + 4 * r;
-          src[xt][r] = !m_valid<S>(xt, r, lr) ? 0.0 : kd.kind == 1 ? row[y] : Lb[(int64_t)(c * S + y) * kTile];
+          src[xt][r] = !m_valid<S>(xt, r, lr) ? 0.0 : (kd.kind == 1 ? row[y] : Lb[(int64_t)(c * S + y) * kTile]) * sc[j];
         }
       mvs(d, src, a.pmatsT + ((size_t)kd.node * C + c) * S * S);
     };
@@ -252,7 +314,7 @@ __global__ __launch_bounds__(kNniThreads) __attribute__((amdgpu_waves_per_eu(S =
           for (int r = 0; r < 4; ++r) {
             const int y = 16 * xt + lr + 4 * r;
             const bool v = m_valid<S>(xt, r, lr);
-            const double u = v ? Ub[(int64_t)(c * S + y) * kTile] : 0.0;
+            const double u = v ? Ub[(int64_t)(c * S + y) * kTile] * sc[5] : 0.0;
             w1[xt][r] = v && mv.g_pi ? u * a.pi[y] : u;
           }
         mvs(up, w1, a.pmats + ((size_t)mv.g_node * C + c) * S * S);

@@ -418,6 +418,11 @@ int plk_branch_counts(plk_handle h, int n_branches, const int32_t* branches,
  *   delta(t) = sum_p w_p log rho(t) = lnL(swapped tree, branch p of length t) - lnL(current tree),
  *   d1 = sum_p w_p rho'/rho,   d2 = sum_p w_p (rho''/rho - (rho'/rho)^2).
  * l_cur and gamma come from the same stored vectors, so scale counts cancel and are never read.
+ * Before the product an exact power of two (the exponent of its joint maximum over classes and
+ * states) is taken out of each of those vectors -- U_g and the L of s, u, the third son of g and
+ * the other sons of p -- so the product of four to six vectors that PLK_FLAG_SCALING leaves
+ * anywhere in [2^-256, 1) stays a normal double; l_cur, gamma and d share the factor and results
+ * are bitwise those of the plain product wherever that one did not underflow.
  * The matrix-vector products are paid once per move; every trial length is one streaming pass
  * over C S + 2 coefficients per pattern.  While t max|lambda_k r_c| <= 1, rho is summed as
  * d + sum gamma expm1(lambda r t) with d = sum_c p_c A1 . A2 / l_cur = sum gamma, which is formed
@@ -446,8 +451,13 @@ int plk_branch_counts(plk_handle h, int n_branches, const int32_t* branches,
  * (NNITopologySearch.cpp:97-212) at once.  Deviations:
  *   - Newton to `tol` in the place of Brent at tolerance 0.1: t_opt is closer to the optimum and
  *     delta at least as large.  The reference returns -delta.
- *   - A pattern whose l_cur or rho is not a positive finite number (an unscaled underflow) adds 0
- *     to all three sums and raises no error, as posteriors and mapping have it.
+ *   - A pattern whose l_cur or rho is not a positive finite number adds 0 to all three sums and
+ *     raises no error, as posteriors and mapping have it.  With the powers of two taken out as
+ *     above, l_cur is zero only where one of the stored vectors is zero in every class and
+ *     state: a pattern the traversal itself lost (an underflow of a handle without
+ *     PLK_FLAG_SCALING; -inf or 0 weight in plk_root_loglik's site_lnl) or one the data make
+ *     impossible on the current tree.  No product of stored vectors that are each representable
+ *     drops a pattern; l_cur is never a denormal number short of that.
  *   - Real eigen systems only; p and g of at most three sons.
  * PLK_ERR_STATE without PLK_FLAG_DOUBLE_RECURSIVE, before a traversal, without dP / d2P (the
  * preorder pass demands them) or for a model without an eigen system; PLK_ERR_UNSUPPORTED with
@@ -494,7 +504,9 @@ int plk_site_row_from_root(plk_handle h, int root, int row, int64_t* n_bad);
 /* Row first_row + i receives log rho_i(t_i) per pattern for the move (son[i], uncle[i]): exactly
  * the terms plk_nni_scores weights and sums into delta at max_iter == 0, t0 = t (the same
  * coefficient build, the same short-length expm1 form under the same condition); a pattern whose
- * l_cur or rho is not a positive finite number gets 0.0.  So lnL_site(swapped tree, branch p of
+ * l_cur or rho is not a positive finite number gets 0.0 -- as in plk_nni_scores only a pattern
+ * that the traversal itself lost (a stored vector of zeros), never one whose stored vectors are
+ * each representable and merely small.  So lnL_site(swapped tree, branch p of
  * length t_i) = lnL_site(current tree) + row.  Preconditions, error codes, the reuse of an
  * up-to-date preorder pass, the staging bound (2 GiB, PLK_TUNE NNI_CAP_KB) and multi-device
  * behaviour are those of plk_nni_scores; t_i must be positive and finite (PLK_ERR_ARG). */

@@ -254,7 +254,9 @@ def test_counts_nonhomogeneous_rooted():
 
 
 def test_counts_deep_caterpillar_rescaled():
-    """300 taxa: L and U pass through rescaling; the scale counts cancel in n_k / l."""
+    """300 taxa: L and U pass through rescaling; the scale counts cancel in n_k / l.  (While the
+    product of the stored vectors is a normal double: n_k multiplies two of them; group G of
+    test_gpu_xref_consumers.py holds the products of four to six.)"""
     et = phylo.engine_tree(_caterpillar(300, lo=0.1, hi=0.4))
     m, rates, probs, states = _dna_case(et, 200, 5)
     B = phylo.comprehensive_register(m.Q)

@@ -171,7 +171,9 @@ def test_fixed_length_mfma(S, C, tree, n_pat):
 
 def test_deep_caterpillar_rescaled():
     """300 taxa: L and U pass through rescaling and underflow doubles without it; the scale
-    counts cancel in gamma / l_cur.  Against the oracle with scaling on both topologies, t = 1e-6
+    counts cancel in gamma / l_cur (while the product of the four to six stored vectors is a
+    normal double: here every sibling and uncle is a tip; the coefficient build takes a power
+    of two out of each vector for the other case, group G of test_gpu_xref_consumers.py).  Against the oracle with scaling on both topologies, t = 1e-6
     (the short-length form on rescaled L and U) included.  The restatement has no rescaling, so
     d1 and d2 are checked against fourth-order central differences of that oracle (h = 0.01 t,
     as t d1 and t^2 d2 per unit weight, bounds 1e-6 and 1e-5: test_nni_cpu.py's reasoning, the

@@ -285,7 +285,9 @@ def test_posteriors_polytomy():
 
 def test_posteriors_deep_caterpillar_rescaled():
     """300 taxa: lower partials and upper vectors pass through rescaling; the scale counts
-    cancel in J / l and are never read."""
+    cancel in J / l and are never read.  (That holds while the product of the stored vectors
+    is a normal double: J multiplies two of them, each above 2^-512, so it does here; where
+    four to six meet -- branch terms, NNI -- see group G of test_gpu_xref_consumers.py.)"""
     m = phylo.gtr(1.2, 0.4, 0.6, 0.8, 0.5, 0.3, 0.2, 0.25, 0.25)
     rates, probs = phylo.gamma_rates(4, 0.5)
     et = phylo.engine_tree(_caterpillar(300, lo=0.1, hi=0.4))

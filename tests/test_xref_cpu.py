@@ -1,7 +1,9 @@
-"""The extended-range reference (tests/xref.py) checked before tests/test_gpu_xref.py relies
-on it: against the fp64 oracle where the oracle has the quantity, against central differences
-of its own longdouble lnL where it has not (root pairs, per-branch models), and against three
-planted errors that it must be able to tell from the truth.
+"""The extended-range reference (tests/xref.py) checked before tests/test_gpu_xref.py and
+tests/test_gpu_xref_consumers.py rely on it: against the fp64 oracle where the oracle has the
+quantity, against central differences of its own longdouble lnL where it has not (root pairs,
+per-branch models), posteriors, counts and NNI scores against the fp64 references of the
+consumers' own GPU tests, and against planted errors that it must be able to tell from the
+truth.
 
 Measured on the CPU (the worst over the cases of each test; every test prints its own):
   per-pattern lnL vs oracle.tree_loglik, relative      2.7e-16 unscaled, 2.7e-16 scaled  (bound 1e-13)
@@ -12,7 +14,23 @@ Measured on the CPU (the worst over the cases of each test; every test prints it
     up to 4.9e-7 in d1 from truncation alone)
   planted errors, smallest move of d2 in the _close metric (they must pass 1e-10):
     2 alpha beta -> alpha beta 1.7e-2, g^2 dropped 1.2, d2P of one branch times (1 + 1e-8) 5.4e-10
+  posteriors vs the clamping reference, absolute             6.7e-16                      (bound 1e-13)
+  counts vs plain pruning on Van Loan's W, / max(1, |ref|)   2.1e-15                      (bound 2e-13)
+  NNI delta vs test_nni_cpu.Pruning, weight sums             3.8e-14                      (bound 1e-12)
+  NNI d1 / d2 vs test_nni_cpu.Restatement, / max(wsum, |ref|)
+    the fp64 restatement                                     1.0e-14 / 1.7e-14            (bound 1e-12)
+    the same restatement held in longdouble                  2.7e-18 / 6.7e-18            (bound 5e-16)
+    (with the trial P in the unit form I + V expm1(lambda r t) Vinv, xref.eigen_matrices.  With
+    V exp(lambda r t) Vinv the restatement, which sums the short-length form d + sum gamma expm1,
+    was 5.8e-12 / 1.1e-11 away at t = 1e-6, 7.4e-11 weight sums in d1 on 64 states, in doubles and
+    in longdouble alike: V Vinv - I of an eigen system held in doubles, not rounding.)
+  planted errors in the consumers (they must pass 1e-10): a sibling left out of up_v moves a joint
+    posterior by 0.52, W of one type times (1 + 1e-8) a count by 8.8e-9 (the total per weight by
+    2.9e-10), the pair swapped in p's son list only delta by at least 0.12 weight sums
+  the seeds of the GPU cases: no best_state cell inside the 1e-8 gap; group G regimes 60 % to 92 %
 """
+from types import SimpleNamespace
+
 import numpy as np
 import pytest
 
@@ -20,7 +38,12 @@ import oracle
 import phylo
 import workload
 import xref
+import test_nni_cpu as nni_ref
+from test_count_matrices_cpu import van_loan
+from test_gpu_mapping import _pruning_counts
 from test_gpu_parity import _random_problem
+from test_gpu_posteriors import _clamp_joint
+from test_gpu_posteriors import _lower as _fp64_lower
 
 LD = np.longdouble
 PAIRS = ((0.3, 0.7), (0.25, -0.25), (1.0, 0.0), (0.0, 1.0))
@@ -289,3 +312,241 @@ def test_planted_errors_are_caught():
     assert _close_err(xb.d2[a], x.d2[a]) > GPU_TOL
     others = [v for v in range(et.n_nodes) if v not in (a, et.root)]
     assert all(xb.d2[v] == x.d2[v] for v in others) and np.array_equal(xb.d1, x.d1)
+
+
+# ---------------------------------------------------------------- posteriors, counts, NNI
+
+CONSUMER_SHAPES = SHAPES[:4]
+
+
+def _consumer_problem(case):
+    if case == "poly":
+        return _poly_problem(300)
+    S, C, n_taxa, n_pat, amb = CONSUMER_SHAPES[case]
+    return _random_problem(S, C, n_taxa, n_pat, seed=100 + S + C, amb=amb)
+
+
+def _internal(et):
+    return list(range(et.n_tips, et.n_nodes))
+
+
+def _branches(et):
+    return [v for v in range(et.n_nodes) if v != et.root]
+
+
+def _all_moves(et):
+    """Every (son, uncle) whose father is not the root, whatever the number of sons (the
+    reference serves the polytomies the engine leaves out)."""
+    sons, par = nni_ref.sons_of(et.ops), nni_ref.parents_of(et.ops)
+    return [(s, u) for s in sorted(par) if par[s] != et.root for u in sons[par[par[s]]] if u != par[s]]
+
+
+@pytest.mark.parametrize("case", list(range(len(CONSUMER_SHAPES))) + ["poly"])
+def test_posteriors_vs_clamping(case):
+    """joint, state and class posteriors of every internal node against the clamping
+    reference of test_gpu_posteriors.py (fp64: prune with L_v zeroed except at x)."""
+    et, m, alph, rates, probs, states = _consumer_problem(case)
+    P, _, _ = _oracle_matrices(et, m, rates)
+    nodes = _internal(et)
+    x = xref.posteriors(et, states, alph.init_table, P, probs, m.pi, nodes)
+    L = _fp64_lower(et, states, alph.init_table, P)
+    worst = 0.0
+    for i, v in enumerate(nodes):
+        J = _clamp_joint(et, L, P, probs, m.pi, v)
+        J = J / J.sum(axis=(1, 2))[:, None, None]
+        worst = max(worst, float(np.abs(x.joint[i] - J).max()), float(np.abs(x.states[i] - J.sum(axis=1)).max()),
+                    float(np.abs(x.classes[i] - J.sum(axis=2)).max()))
+        assert np.array_equal(x.best[i], x.states[i].argmax(axis=1))
+    _note("posteriors", worst)
+    assert worst <= 1e-13
+    assert float(np.abs(x.joint.sum(axis=(2, 3)) - 1).max()) <= 1e-17
+
+
+@pytest.mark.parametrize("case", list(range(len(CONSUMER_SHAPES))) + ["poly"])
+def test_counts_vs_pruning(case):
+    """Counts of every branch against _pruning_counts of test_gpu_mapping.py with Van Loan's W
+    (DNA: the twelve comprehensive types; 20 and 64 states: the total register)."""
+    et, m, alph, rates, probs, states = _consumer_problem(case)
+    P, _, _ = _oracle_matrices(et, m, rates)
+    B = phylo.comprehensive_register(m.Q) if m.S == 4 else phylo.total_register(m.Q)
+    br = _branches(et)
+    W = {v: np.stack([van_loan(m.Q, B, et.brlen[v] * r) for r in rates], axis=1) for v in br}
+    x = xref.branch_counts(et, states, alph.init_table, P, W, probs, m.pi, br)
+    L = _fp64_lower(et, states, alph.init_table, P)
+    worst = 0.0
+    for i, v in enumerate(br):
+        ref = _pruning_counts(et, L, P, W, probs, m.pi, v)
+        worst = max(worst, float((np.abs(x.counts[i] - ref) / np.maximum(1.0, np.abs(ref))).max()))
+    _note("counts", worst)
+    assert worst <= 2e-13
+    assert np.array_equal(x.totals, x.counts.sum(axis=1))
+
+
+def _trial(m, rates, t):
+    mats = [xref.trial_matrices(m.V, m.Vinv, m.lam, ti, rates) for ti in t]
+    return tuple([mm[k] for mm in mats] for k in range(3))
+
+
+@pytest.mark.parametrize("case", list(range(len(CONSUMER_SHAPES))) + ["poly"])
+def test_nni_vs_pruning_and_restatement(case):
+    """delta of every move against test_nni_cpu.Pruning (the oracle on the swapped son arrays) at
+    t_cur, t_cur / 2, 1e-6 and 3; d1 and d2 against test_nni_cpu.Restatement (the engine's
+    gamma / eigen formulation in numpy), d2 relative as in test_gpu_nni.py."""
+    et, m, alph, rates, probs, states = _consumer_problem(case)
+    P, _, _ = _oracle_matrices(et, m, rates)
+    P[et.root] = np.eye(m.S)[None]
+    moves = _all_moves(et)
+    if len(moves) > 12:
+        moves = moves[::len(moves) // 12]
+    par = nni_ref.parents_of(et.ops)
+    rng = np.random.default_rng(7)
+    w = rng.integers(1, 9, states.shape[1]).astype(np.float64)
+    wsum = w.sum()
+    args = (states, alph.init_table, P, rates, probs, m.pi, m, w)
+    pr = nni_ref.Pruning(et.ops, et.root, et.n_nodes, et.n_tips, *args)
+    rs = nni_ref.Restatement(et.ops, et.root, et.n_tips, *args)
+    ml = SimpleNamespace(V=m.V.astype(LD), Vinv=m.Vinv.astype(LD), lam=m.lam.astype(LD))
+    rl = nni_ref.Restatement(et.ops, et.root, et.n_tips, states, alph.init_table, P.astype(LD), rates.astype(LD),
+                             probs.astype(LD), m.pi.astype(LD), ml, w.astype(LD))
+    t_cur = np.array([et.brlen[par[s]] for s, _ in moves])
+    for t0 in (t_cur, 0.5 * t_cur, np.full(len(moves), 1e-6), np.full(len(moves), 3.0)):
+        x = xref.nni(et, states, alph.init_table, P, probs, m.pi, moves, *_trial(m, rates, t0), weights=w)
+        r = rs.scores(moves, t0)
+        for i, (s, u) in enumerate(moves):
+            _, l1, l2 = _evaluate_ld(rl, s, u, t0[i])
+            ed = abs(float(x.delta[i]) - pr.delta(s, u, t0[i])) / wsum
+            e1 = float(abs(x.d1[i] - l1)) / max(wsum, abs(r["d1"][i]))
+            e2 = float(abs(x.d2[i] - l2)) / max(wsum, abs(r["d2"][i]))
+            f1 = abs(float(x.d1[i]) - r["d1"][i]) / max(wsum, abs(r["d1"][i]))
+            f2 = abs(float(x.d2[i]) - r["d2"][i]) / max(wsum, abs(r["d2"][i]))
+            fa = abs(float(x.d1[i]) - r["d1"][i]) / wsum
+            for key, v in (("nni delta", ed), ("nni d1", e1), ("nni d2", e2), ("nni d1 fp64", f1), ("nni d2 fp64", f2),
+                           ("nni d1 fp64 per weight", fa)):
+                _note(key, v)
+            assert max(ed, f1, f2) <= 1e-12 and max(e1, e2) <= 5e-16, (s, u, t0[i], ed, e1, e2, f1, f2)
+
+
+def _evaluate_ld(rl, s, u, t):
+    """test_nni_cpu.evaluate of a Restatement held in longdouble, the sums left in longdouble
+    (evaluate itself returns Python floats)."""
+    gam, d = rl.coefficients(s, u)
+    mu = rl.rates[:, None] * rl.model.lam[None, :]
+    e = np.exp(mu * LD(t))
+    r0 = d + np.einsum("pck,ck->p", gam, np.expm1(mu * LD(t)))   # the short-length form at every t
+    g1 = np.einsum("pck,ck->p", gam, e * mu) / r0
+    g2 = np.einsum("pck,ck->p", gam, e * mu * mu) / r0
+    return (rl.w * np.log(r0)).sum(), (rl.w * g1).sum(), (rl.w * (g2 - g1 * g1)).sum()
+
+
+def test_planted_errors_in_the_consumers_are_caught():
+    """Each new function tells a planted error from the truth at the GPU tests' tolerance: a
+    sibling left out of up_v (posteriors, 1e-10 absolute), W of one type times 1 + 1e-8 (counts,
+    1e-10 max(1, |ref|)), the pair swapped in the son list of p but not of g (NNI delta,
+    1e-10 weight sums)."""
+    et, m, alph, rates, probs, states = _consumer_problem(0)
+    P, _, _ = _oracle_matrices(et, m, rates)
+    n, C, S = states.shape[1], len(rates), m.S
+    # a sibling left out of up_v
+    sons, par = nni_ref.sons_of(et.ops), nni_ref.parents_of(et.ops)
+    v = next(v for v in _internal(et) if v != et.root)
+    sib = next(o for o in sons[par[v]] if o != v)
+    x = xref.posteriors(et, states, alph.init_table, P, probs, m.pi, [v])
+    Pl, pl, pil = xref._ld(P), xref._ld(probs), xref._ld(m.pi)
+    L, q = xref._lower(et, states, alph.init_table, Pl)
+    q_bad = dict(q)
+    q_bad[sib] = np.ones((n, C, S), dtype=LD)
+    _, up = xref._father_sides(et, q_bad, pil, Pl, n, C, S, [v])
+    J = pl[None, :, None] * L[v] * up[v]
+    J = J / J.sum(axis=(1, 2))[:, None, None]
+    move = float(np.abs(J - x.joint[0]).max())
+    print(f"plant sibling: moves joint by {move:.3g}")
+    FLOORS["plant sibling"] = move
+    assert move > GPU_TOL
+    # W of one type larger by 1e-8
+    B = phylo.comprehensive_register(m.Q)
+    br = _branches(et)
+    W = {b: np.stack([van_loan(m.Q, B, et.brlen[b] * r) for r in rates], axis=1) for b in br}
+    W_bad = {b: W[b].astype(LD) for b in br}
+    for b in br:
+        W_bad[b][3] *= LD(1) + LD("1e-8")
+    c = xref.branch_counts(et, states, alph.init_table, P, W, probs, m.pi, br)
+    cb = xref.branch_counts(et, states, alph.init_table, P, W_bad, probs, m.pi, br)
+    wsum = LD(n)
+    move = float((np.abs(cb.totals - c.totals) / wsum / np.maximum(1.0, np.abs(c.totals) / wsum)).max())
+    movec = float((np.abs(cb.counts - c.counts) / np.maximum(1.0, np.abs(c.counts))).max())
+    print(f"plant W: moves counts by {movec:.3g}, totals / weight sum by {move:.3g}")
+    FLOORS["plant W"] = movec
+    assert movec > GPU_TOL
+    others = [k for k in range(12) if k != 3]
+    assert np.array_equal(cb.counts[:, :, others], c.counts[:, :, others])
+    # the swapped pair not swapped in the son list of g
+    moves = _all_moves(et)[::5]
+    t_cur = np.array([et.brlen[par[s]] for s, _ in moves])
+    tm = _trial(m, rates, t_cur)
+
+    def half_swap(sons, par, s, u):
+        p = par[s]
+        return {p: [u if o == s else o for o in sons[p]]}
+
+    good = xref.nni(et, states, alph.init_table, P, probs, m.pi, moves, *tm)
+    bad = xref.nni(et, states, alph.init_table, P, probs, m.pi, moves, *tm, swap=half_swap)
+    move = float(np.abs(bad.delta - good.delta).min() / wsum)
+    print(f"plant half swap: moves delta by at least {move:.3g} weight sums")
+    FLOORS["plant half swap"] = move
+    assert move > GPU_TOL
+
+
+# ---------------------------------------------------------------- the GPU cases, as far as the CPU can judge them
+
+def _eigen_P(case):
+    """fp64 V exp(lambda r t) Vinv of every branch (the engine's own matrices differ in the last
+    digits: nothing here is that sensitive)."""
+    et = case.et
+    P = np.zeros((et.n_nodes, case.C, case.S, case.S))
+    for v in case.br:
+        m = case.models[0 if case.mon is None else int(case.mon[v])]
+        P[v] = np.stack([m.pij(r * et.brlen[v]) for r in case.rates])
+    return P
+
+
+def _gpu_cases():
+    import test_gpu_xref_consumers as cons
+    from test_gpu_posteriors import _six_nodes
+    from test_gpu_xref import _case_bc1, _case_deep, _case_very_deep
+    yield "E C=3", _case_very_deep(4, 3), _six_nodes
+    yield "E C=8", _case_very_deep(4, 8), _six_nodes
+    yield "F S=20", _case_deep(20), _six_nodes
+    yield "F S=64", _case_deep(64), _six_nodes
+    yield "H flat", _case_bc1(False), _internal
+    yield "H scaled", _case_bc1(True), _internal
+    for name in sorted(cons.G_CASES):
+        yield "G " + name, cons._case_g(name), _internal
+
+
+@pytest.mark.parametrize("group", ["E C=3", "E C=8", "F S=20", "F S=64", "H flat", "H scaled", "G binary-C4", "G binary-C8",
+                                   "G poly-C4", "G tri-C4", "G tri-C8", "G tri-S20"])
+def test_gpu_cases_best_state_and_regime(group):
+    """The seeds of tests/test_gpu_xref_consumers.py: the reference alone leaves at most 1 % of the
+    best_state cells inside the 1e-8 gap; the group G cases reach their regime (the product of
+    the stored vectors' joint maxima below 2^-1022 on a quarter of the patterns) while the lower
+    pass, carried out by the traversal's rule, keeps every stored partial a normal double."""
+    import test_gpu_xref_consumers as cons
+    case, pick = next(c[1:] for c in _gpu_cases() if c[0] == group)
+    P = _eigen_P(case)
+    low = xref.lower(case.et, case.states, case.alph.init_table, P)
+    nodes = pick(case.et)
+    x = xref.posteriors(case.et, case.states, case.alph.init_table, P, case.probs, case.pi, nodes, lower=low)
+    top = np.sort(x.states, axis=2)
+    skipped = 1.0 - float(np.asarray(top[:, :, -1] - top[:, :, -2] > 1e-8).mean())
+    print(f"{group}: best_state cells inside the 1e-8 gap {skipped:.2%}, smallest likelihood 2^{float(np.log2(x.l.min())):.0f}")
+    assert skipped <= 0.01
+    if not group.startswith("G "):
+        return
+    Lmax, Umax, Ls = cons._stored(case, P, low)
+    (mv_share, mv), (f_share, f) = cons._regime(case, Lmax, Umax)
+    print(f"{group}: regime on {mv_share:.0%} of the patterns at the move {mv}, {f_share:.0%} at the father {f}")
+    want_move, want_father = {"binary": (True, False), "tri": (True, True), "poly": (False, True)}[group.split()[1].split("-")[0]]
+    assert (mv_share >= 0.25 or not want_move) and (f_share >= 0.25 or not want_father)
+    for v in range(case.et.n_tips, case.et.n_nodes):
+        m = Ls[v].max(axis=(1, 2))
+        assert np.all((m == 0) | (m >= LD(2) ** -1022)), v
