@@ -573,10 +573,14 @@ __global__ __launch_bounds__(kDrThreads) void dr_pre_s4_kernel(const DrPreOp* __
   if (SCALE)
 #pragma unroll
     for (int i = 0; i < 3; ++i)
-      if (i < op.n && op.uslot[i] >= 0 && umax[i] > 0.0 && umax[i] < kScaleThr) {
+      if (i < op.n && op.uslot[i] >= 0) {
+        // until the joint maximum is back in [2^-256, 1): U_f and two sons' stored q multiply
+        // to as little as 2^-768
         double* dst = uout + (int64_t)op.uslot[i] * a.slot_stride + tb;
+        for (double m = umax[i]; m > 0.0 && m < kScaleThr; m *= kScaleUp) {
 #pragma unroll
-        for (int e = 0; e < C * S; ++e) dst[(int64_t)e * kTile] *= kScaleUp;
+          for (int e = 0; e < C * S; ++e) dst[(int64_t)e * kTile] *= kScaleUp;
+        }
       }
   const int wv = threadIdx.x >> 6;
 #pragma unroll
@@ -796,7 +800,8 @@ __global__ __launch_bounds__(256) void dr_pre_m20_kernel(const DrPreOp* __restri
       double m = umax[i];
       m = fmax(m, __shfl_xor(m, 16, 64));
       m = fmax(m, __shfl_xor(m, 32, 64));
-      if (m > 0.0 && m < kScaleThr) {
+      // until the joint maximum is back in [2^-256, 1) (down to 2^-768 before the first step)
+      for (; m > 0.0 && m < kScaleThr; m *= kScaleUp) {
         double* dst = a.uout + (int64_t)op.uslot[i] * a.slot_stride + tb;
         for (int c = 0; c < C; ++c)
 #pragma unroll

@@ -247,6 +247,22 @@ __device__ __forceinline__ void rescale(double (&v)[4 * CW * PW], int (&cnt)[PW]
 #pragma unroll
         for (int i = 0; i < 4 * CW; ++i) v[4 * CW * pw + i] *= kScaleUp;
         cnt[pw] += 1;
+        // until the joint maximum is back in [2^-256, 1): three stored vectors multiply to as
+        // little as 2^-768.  One step adds 0x10000000 to the high word of a normal double, so
+        // the common case (one step was enough) costs one integer compare; the rest is cold
+        // (a loop that formed the high-word maximum again on every trip cost 10 % on the
+        // 512-taxon NH-GTR configuration).
+        if (__builtin_expect(!(hi_decides(mh) && mh + 0x10000000 >= kThrHi), 0)) {
+          double m = 0.0;
+#pragma unroll
+          for (int i = 0; i < 4 * CW; ++i) m = fmax(m, v[4 * CW * pw + i]);
+          while (m > 0.0 && m < kScaleThr) {
+#pragma unroll
+            for (int i = 0; i < 4 * CW; ++i) v[4 * CW * pw + i] *= kScaleUp;
+            cnt[pw] += 1;
+            m *= kScaleUp;
+          }
+        }
       }
     }
     return;
@@ -274,7 +290,9 @@ __device__ __forceinline__ void rescale(double (&v)[4 * CW * PW], int (&cnt)[PW]
   }
 #pragma unroll
   for (int pw = 0; pw < PW; ++pw)
-    if (m[pw] > 0.0 && m[pw] < kScaleThr) {
+    // (every wave of the group read the same m from the exchange buffer: the loop runs on
+    // that register value and needs no further barrier)
+    for (; m[pw] > 0.0 && m[pw] < kScaleThr; m[pw] *= kScaleUp) {
 #pragma unroll
       for (int i = 0; i < 4 * CW; ++i) v[4 * CW * pw + i] *= kScaleUp;
       cnt[pw] += 1;
@@ -903,9 +921,10 @@ inline std::string jit_tree4_source(const JitPlan& plan, const JitShape& sh) {
           v[c][y] = ra[(c * U_ + ca) * 4 + y] * rb[(c * U_ + cb) * 4 + y];
           m = fmax(m, v[c][y]);
         }
-      const bool up = m > 0.0 && m < kScaleThr;
+      int up = 0;  // steps of 2^256 until the joint maximum is back in [2^-256, 1)
+      for (; m > 0.0 && m < kScaleThr; m *= kScaleUp) ++up;
       for (int c = 0; c < C_; ++c) {
-        if (up)
+        for (int k_ = 0; k_ < up; ++k_)
           for (int y = 0; y < 4; ++y) v[c][y] *= kScaleUp;
         for (int x = 0; x < 4; ++x) {
           const double* P = pmats + ((i64)ud.br * C_ + c) * 16 + 4 * x;
@@ -916,7 +935,7 @@ inline std::string jit_tree4_source(const JitPlan& plan, const JitShape& sh) {
           dst[c * (U_ * U_ * 4) + TABIX(U_ * U_, r, x)] = t2;
         }
       }
-      reinterpret_cast<u8*>(tab + ud.koff)[r] = up ? 1 : 0;
+      reinterpret_cast<u8*>(tab + ud.koff)[r] = (u8)up;
     }
   }
   // the other tables: wave w stages units w, w + NWT_, ... of the fragment's other-unit list
@@ -1332,6 +1351,20 @@ inline std::string jit_tree4_source(const JitPlan& plan, const JitShape& sh) {
           snprintf(buf, sizeof(buf), "      flag_risky(dng, A%d);\n", d);
         s += buf;
       };
+      // the checks inside a node of more than three sons (plk_tree4.hpp: scale_check_after),
+      // at the interpreter's sons; every wave of the workgroup runs the same straight-line
+      // code, so all of them reach such a check's barrier.  `sons` sons of the node at
+      // `level` came in with event i; the node's end has its own check.
+      std::vector<int> nsons((size_t)max_level + 1, 0);
+      auto mid_check = [&](int level, int sons, size_t i) {
+        for (int k = 0; k < sons; ++k) {
+          const bool due = scale_check_after(++nsons[(size_t)level]);
+          // (a pair unit holds the first two sons of its node: no check falls between them)
+          if (due && k + 1 == sons && sh.scale && i + 1 < ev.size() && ev[i + 1].op != T_ASCEND &&
+              ev[i + 1].op != T_ROOT)
+            check_line(level);
+        }
+      };
       for (size_t i = 0; i < ev.size(); ++i) {
         const JitEvent& e = ev[i];
         if (e.op == T_TIP || e.op == T_LOAD) {
@@ -1362,9 +1395,14 @@ inline std::string jit_tree4_source(const JitPlan& plan, const JitShape& sh) {
             snprintf(buf, sizeof(buf), "      kadd(K%d, FK%d);\n", e.level, slot[i]);
             s += buf;
           }
+          {
+            const JitUnit* u = e.op == T_TIP ? &plan.units[f][(size_t)e.a] : nullptr;
+            mid_check(e.level, u && u->tb >= 0 && u->br < 0 ? 2 : 1, i);
+          }
           s += "      SB\n";
         } else if (e.op == T_DESCEND) {
           fresh[(size_t)e.level] = 1;
+          nsons[(size_t)e.level] = 0;
           snprintf(buf, sizeof(buf), "      kzero(K%d);\n", e.level);
           s += buf;
         } else if (e.op == T_ASCEND) {
@@ -1388,6 +1426,7 @@ inline std::string jit_tree4_source(const JitPlan& plan, const JitShape& sh) {
             snprintf(buf, sizeof(buf), "      kadd(K%d, K%d);\n", dd - 1, dd);
             s += buf;
           }
+          mid_check(dd - 1, 1, i);
           s += "      SB\n";
         } else {  // T_ROOT
           if (sh.scale) check_line(0);

@@ -224,16 +224,18 @@ inline std::string jit_treeM4_source(const std::vector<TInstr>& prog, const std:
 // joint exact power-of-two rescale of the pattern (its states sit in lanes hi = 0..3)
 // (the hi-word max is the same in the four lanes of a pattern, so a fallback to the f64
 // max runs with all four active)
-#define RESCALE(V, K) { int mh_ = 0; bool up_; \
+// (until the joint maximum is back in [2^-256, 1): three stored vectors multiply to as little
+// as 2^-768, so the check is made again on the stepped values)
+#define RESCALE(V, K) for (;;) { int mh_ = 0; bool up_; \
   _Pragma("unroll") for (int c_ = 0; c_ < C_; ++c_) _Pragma("unroll") for (int X_ = 0; X_ < XB_; ++X_) mh_ = max(mh_, hiw(V[c_][X_])); \
   mh_ = max(mh_, __shfl_xor(mh_, 16, 64)); mh_ = max(mh_, __shfl_xor(mh_, 32, 64)); \
   if (__builtin_expect(hi_decides(mh_), 1)) { up_ = mh_ < kThrHi; } else { double m_ = 0.0; \
     _Pragma("unroll") for (int c_ = 0; c_ < C_; ++c_) _Pragma("unroll") for (int X_ = 0; X_ < XB_; ++X_) m_ = fmax(m_, V[c_][X_]); \
     m_ = fmax(m_, __shfl_xor(m_, 16, 64)); m_ = fmax(m_, __shfl_xor(m_, 32, 64)); \
     up_ = m_ > 0.0 && m_ < kScaleThr; } \
-  if (up_) { \
-    _Pragma("unroll") for (int c_ = 0; c_ < C_; ++c_) _Pragma("unroll") for (int X_ = 0; X_ < XB_; ++X_) V[c_][X_] *= kScaleUp; \
-    K += 1; } }
+  if (__builtin_expect(!up_, 1)) break; \
+  _Pragma("unroll") for (int c_ = 0; c_ < C_; ++c_) _Pragma("unroll") for (int X_ = 0; X_ < XB_; ++X_) V[c_][X_] *= kScaleUp; \
+  K += 1; }
 // root reduction (RHomogeneousTreeLikelihood.cpp:162-216 / NH :168-233) and the fixed
 // butterfly over each 64 patterns of the workgroup (root_kernel's order)
 #define REDUCE_ROOT(V, K) { double l_ = 0.0; \
@@ -453,6 +455,17 @@ inline std::string jit_treeM4_source(const std::vector<TInstr>& prog, const std:
     std::vector<char> fresh((size_t)max_level + 2, 0);
     fresh[0] = 1;
     int d = 0;
+    // the checks inside a node of more than three sons (plk_tree4.hpp: scale_check_after), at
+    // the interpreter's sons; RESCALE has no barrier.  Event i brought one son into the node
+    // at `level`; the node's end has its own check.
+    std::vector<int> nsons((size_t)max_level + 2, 0);
+    auto mid_check = [&](int level, size_t i) {
+      if (scale_check_after(++nsons[(size_t)level]) && sh.scale && i + 1 < ev.size() && ev[i + 1].op != T_ASCEND &&
+          ev[i + 1].op != T_ROOT) {
+        snprintf(buf, sizeof(buf), "    RESCALE(A%d, K%d)\n", level, level);
+        s += buf;
+      }
+    };
     for (size_t i = 0; i < ev.size(); ++i) {
       const TInstr& e = ev[i];
       if (e.op == T_CHERRY || e.op == T_TIP || e.op == T_LOAD) {
@@ -481,10 +494,12 @@ inline std::string jit_treeM4_source(const std::vector<TInstr>& prog, const std:
           }
         }
         fresh[(size_t)d] = 0;
+        mid_check(d, i);
         s += "    SB\n";
       } else if (e.op == T_DESCEND) {
         ++d;
         fresh[(size_t)d] = 1;
+        nsons[(size_t)d] = 0;
         snprintf(buf, sizeof(buf), "    K%d = 0;\n", d);
         s += buf;
       } else if (e.op == T_ASCEND) {
@@ -506,6 +521,7 @@ inline std::string jit_treeM4_source(const std::vector<TInstr>& prog, const std:
         }
         fresh[(size_t)d - 1] = 0;
         --d;
+        mid_check(d, i);
         s += "    SB\n";
       } else {  // T_ROOT
         if (sh.scale) s += "    RESCALE(A0, K0)\n";

@@ -134,9 +134,10 @@ __global__ __launch_bounds__(256) void partials_s4_kernel(const KOp* __restrict_
         cnt.y += sc.y;
       }
     }
-  }
-
-  if (SCALE) {
+    // the check: at the op's end and, in an ACCUMULATE op (the running product of the sons so
+    // far is one factor already), after its second son, so that at most three stored vectors
+    // enter the product between two checks (plk_tree4.hpp: scale_check_after)
+    if (!SCALE || !(k == n - 1 || ((op.flags & 1) && k == 1))) continue;
     const bool sg = (op.flags & kOpSigned) != 0;
     double m0 = 0.0, m1 = 0.0;
 #pragma unroll
@@ -146,8 +147,11 @@ __global__ __launch_bounds__(256) void partials_s4_kernel(const KOp* __restrict_
         m0 = fmax(m0, scale_key(acc[c][x].x, sg));
         m1 = fmax(m1, scale_key(acc[c][x].y, sg));
       }
-    const bool r0 = (m0 > 0.0 && m0 < kScaleThr), r1 = (m1 > 0.0 && m1 < kScaleThr);
-    if (r0 || r1) {
+    // until both joint maxima are back in [2^-256, 1): three stored vectors multiply to as
+    // little as 2^-768
+    for (;;) {
+      const bool r0 = (m0 > 0.0 && m0 < kScaleThr), r1 = (m1 > 0.0 && m1 < kScaleThr);
+      if (!(r0 || r1)) break;
 #pragma unroll
       for (int c = 0; c < C; ++c)
 #pragma unroll
@@ -157,9 +161,11 @@ __global__ __launch_bounds__(256) void partials_s4_kernel(const KOp* __restrict_
         }
       cnt.x += r0;
       cnt.y += r1;
+      if (r0) m0 *= kScaleUp;
+      if (r1) m1 *= kScaleUp;
     }
-    reinterpret_cast<int2*>(a.scale + (size_t)op.parent * a.n_pad + (size_t)tile * kTile)[lane] = cnt;
   }
+  if (SCALE) reinterpret_cast<int2*>(a.scale + (size_t)op.parent * a.n_pad + (size_t)tile * kTile)[lane] = cnt;
 #pragma unroll
   for (int c = 0; c < C; ++c)
 #pragma unroll
@@ -252,23 +258,26 @@ __global__ __launch_bounds__(256) void partials_links_s4_kernel(const KOpL* __re
             }
           if (SCALE) cnt += a.scale[(size_t)kd.child * a.n_pad + l];
         }
+        // the joint check after every group of three and, in every group but the first (the
+        // running product is one factor already), after the group's second son, as the
+        // uncompressed traversal's ACCUMULATE ops do: at most three stored vectors enter the
+        // product between two checks
+        if (SCALE && (k == gn - 1 || (g0 > 0 && k == 1))) {
+          double m = 0.0;
+#pragma unroll
+          for (int c = 0; c < C; ++c)
+#pragma unroll
+            for (int x = 0; x < S; ++x) m = fmax(m, acc[c][x]);
+          while (m > 0.0 && m < kScaleThr) {  // until back in [2^-256, 1)
+#pragma unroll
+            for (int c = 0; c < C; ++c)
+#pragma unroll
+              for (int x = 0; x < S; ++x) acc[c][x] *= kScaleUp;
+            cnt += 1;
+            m *= kScaleUp;
+          }
+        }
       }
-    // the joint rescale after every group of three, as the uncompressed traversal's
-    // ACCUMULATE ops do (a wide polytomy's running product never drifts below 2^-256)
-    if (SCALE && j < op.D) {
-      double m = 0.0;
-#pragma unroll
-      for (int c = 0; c < C; ++c)
-#pragma unroll
-        for (int x = 0; x < S; ++x) m = fmax(m, acc[c][x]);
-      if (m > 0.0 && m < kScaleThr) {
-#pragma unroll
-        for (int c = 0; c < C; ++c)
-#pragma unroll
-          for (int x = 0; x < S; ++x) acc[c][x] *= kScaleUp;
-        cnt += 1;
-      }
-    }
   }
   if (j >= op.D) return;
   if (SCALE) a.scale[(size_t)op.parent * a.n_pad + j] = cnt;
@@ -303,7 +312,6 @@ __global__ __launch_bounds__(256) void partials_links_generic_kernel(const KOpL*
   // each group ends with the joint rescale, as the uncompressed traversal's ACCUMULATE ops
   for (int g0 = 0; g0 < n; g0 += kLinkGroup) {
     const int gn = n - g0 < kLinkGroup ? n - g0 : kLinkGroup;
-    double m = 0.0;
     if (g0 > 0) __syncthreads();  // the previous group's tables are read
     for (int k = 0; k < gn; ++k) {
       const KKid& kd = kids[op.k0 + g0 + k];
@@ -320,48 +328,56 @@ __global__ __launch_bounds__(256) void partials_links_generic_kernel(const KOpL*
         const KKid& kd = kids[op.k0 + g0 + k];
         if (!kd.is_tip) cnt += a.scale[(size_t)kd.child * a.n_pad + l[k]];
       }
-    for (int c = 0; c < C; ++c) {
-      for (int x0 = 0; x0 < S; x0 += XB) {
-        double acc[XB];
+    // a group but the first carries the running product as one factor already: it is checked
+    // after its second son as well (sons [0, 2), then [2, gn)), so that at most three stored
+    // vectors enter the product between two checks
+    const int k_mid = (SCALE && g0 > 0 && gn > 2) ? 2 : gn;
+    for (int ka = 0, kb = k_mid; ka < gn; ka = kb, kb = gn) {
+      double m = 0.0;
+      for (int c = 0; c < C; ++c) {
+        for (int x0 = 0; x0 < S; x0 += XB) {
+          double acc[XB];
 #pragma unroll
-        for (int xb = 0; xb < XB; ++xb) acc[xb] = g0 == 0 ? 1.0 : outp[(size_t)(c * S + x0 + xb) * kTile];
-        for (int k = 0; k < gn; ++k) {
-          const KKid& kd = kids[op.k0 + g0 + k];
-          if (kd.is_tip) {
-            const double* t = &lds[k * per + (c * nc + (int)l[k]) * S + x0];
+          for (int xb = 0; xb < XB; ++xb) acc[xb] = (g0 == 0 && ka == 0) ? 1.0 : outp[(size_t)(c * S + x0 + xb) * kTile];
+          for (int k = ka; k < kb; ++k) {
+            const KKid& kd = kids[op.k0 + g0 + k];
+            if (kd.is_tip) {
+              const double* t = &lds[k * per + (c * nc + (int)l[k]) * S + x0];
 #pragma unroll
-            for (int xb = 0; xb < XB; ++xb) acc[xb] *= t[xb];
-          } else {
-            const double* L = a.partials + (size_t)kd.child * a.slot_stride +
-                              (size_t)(l[k] >> 7) * ((size_t)CS * kTile) + (l[k] & 127) + (size_t)c * S * kTile;
-            const double* Pc = &lds[k * per + (c * S + x0) * S];
-            double s[XB];
-            {
-              const double l0 = L[0];
+              for (int xb = 0; xb < XB; ++xb) acc[xb] *= t[xb];
+            } else {
+              const double* L = a.partials + (size_t)kd.child * a.slot_stride +
+                                (size_t)(l[k] >> 7) * ((size_t)CS * kTile) + (l[k] & 127) + (size_t)c * S * kTile;
+              const double* Pc = &lds[k * per + (c * S + x0) * S];
+              double s[XB];
+              {
+                const double l0 = L[0];
 #pragma unroll
-              for (int xb = 0; xb < XB; ++xb) s[xb] = Pc[xb * S] * l0;
-            }
+                for (int xb = 0; xb < XB; ++xb) s[xb] = Pc[xb * S] * l0;
+              }
 #pragma unroll 4
-            for (int y = 1; y < S; ++y) {
-              const double ly = L[(size_t)y * kTile];
+              for (int y = 1; y < S; ++y) {
+                const double ly = L[(size_t)y * kTile];
 #pragma unroll
-              for (int xb = 0; xb < XB; ++xb) s[xb] = __builtin_fma(Pc[xb * S + y], ly, s[xb]);
+                for (int xb = 0; xb < XB; ++xb) s[xb] = __builtin_fma(Pc[xb * S + y], ly, s[xb]);
+              }
+#pragma unroll
+              for (int xb = 0; xb < XB; ++xb) acc[xb] *= s[xb];
             }
+          }
 #pragma unroll
-            for (int xb = 0; xb < XB; ++xb) acc[xb] *= s[xb];
+          for (int xb = 0; xb < XB; ++xb) {
+            if (SCALE) m = fmax(m, acc[xb]);
+            outp[(size_t)(c * S + x0 + xb) * kTile] = acc[xb];
           }
         }
-#pragma unroll
-        for (int xb = 0; xb < XB; ++xb) {
-          if (SCALE) m = fmax(m, acc[xb]);
-          outp[(size_t)(c * S + x0 + xb) * kTile] = acc[xb];
-        }
       }
-    }
-    if (SCALE && m > 0.0 && m < kScaleThr) {
-      for (int i = 0; i < CS; ++i) outp[(size_t)i * kTile] *= kScaleUp;
-      cnt += 1;
-    }
+      if (SCALE)
+        for (; m > 0.0 && m < kScaleThr; m *= kScaleUp) {  // until back in [2^-256, 1)
+          for (int i = 0; i < CS; ++i) outp[(size_t)i * kTile] *= kScaleUp;
+          cnt += 1;
+        }
+    }  // sons [ka, kb)
   }
   if (j >= op.D) return;
   if (SCALE) a.scale[(size_t)op.parent * a.n_pad + j] = cnt;
@@ -407,55 +423,63 @@ __global__ __launch_bounds__(256) void partials_generic_kernel(const KOp* __rest
     if (op.is_tip[k]) code[k] = a.codes[(size_t)op.child[k] * a.n_pad + pidx];
 
   const bool sg = (op.flags & kOpSigned) != 0;
-  double m = 0.0;
-  for (int c = 0; c < C; ++c) {
-    for (int x0 = 0; x0 < S; x0 += XB) {
-      double acc[XB];
-      if (op.flags & 1) {
+  // an ACCUMULATE op carries the running product as one factor already: it is checked after
+  // its second son as well (sons [0, 2), then [2, n)), so that at most three stored vectors
+  // enter the product between two checks (plk_tree4.hpp: scale_check_after)
+  const int k_mid = (SCALE && (op.flags & 1) && n > 2) ? 2 : n;
+  int ka = 0, kb = k_mid;
+  do {
+    double m = 0.0;
+    for (int c = 0; c < C; ++c) {
+      for (int x0 = 0; x0 < S; x0 += XB) {
+        double acc[XB];
+        if ((op.flags & 1) || ka > 0) {
 #pragma unroll
-        for (int xb = 0; xb < XB; ++xb) acc[xb] = outp[(size_t)(c * S + x0 + xb) * kTile];
-      } else {
-#pragma unroll
-        for (int xb = 0; xb < XB; ++xb) acc[xb] = 1.0;
-      }
-      for (int k = 0; k < n; ++k) {
-        if (op.is_tip[k]) {
-          const double* t = &lds[k * per + (c * nc + code[k]) * S + x0];
-#pragma unroll
-          for (int xb = 0; xb < XB; ++xb) acc[xb] *= t[xb];
+          for (int xb = 0; xb < XB; ++xb) acc[xb] = outp[(size_t)(c * S + x0 + xb) * kTile];
         } else {
-          const double* L = a.partials + (size_t)op.child[k] * a.slot_stride + toff + (size_t)c * S * kTile;
-          const double* Pc = &lds[k * per + (c * S + x0) * S];
-          double s[XB];
-          {
-            const double l0 = L[0];
 #pragma unroll
-            for (int xb = 0; xb < XB; ++xb) s[xb] = Pc[xb * S] * l0;
-          }
+          for (int xb = 0; xb < XB; ++xb) acc[xb] = 1.0;
+        }
+        for (int k = ka; k < kb; ++k) {
+          if (op.is_tip[k]) {
+            const double* t = &lds[k * per + (c * nc + code[k]) * S + x0];
+#pragma unroll
+            for (int xb = 0; xb < XB; ++xb) acc[xb] *= t[xb];
+          } else {
+            const double* L = a.partials + (size_t)op.child[k] * a.slot_stride + toff + (size_t)c * S * kTile;
+            const double* Pc = &lds[k * per + (c * S + x0) * S];
+            double s[XB];
+            {
+              const double l0 = L[0];
+#pragma unroll
+              for (int xb = 0; xb < XB; ++xb) s[xb] = Pc[xb * S] * l0;
+            }
 #pragma unroll 4
-          for (int y = 1; y < S; ++y) {
-            const double ly = L[(size_t)y * kTile];
+            for (int y = 1; y < S; ++y) {
+              const double ly = L[(size_t)y * kTile];
 #pragma unroll
-            for (int xb = 0; xb < XB; ++xb) s[xb] = __builtin_fma(Pc[xb * S + y], ly, s[xb]);
+              for (int xb = 0; xb < XB; ++xb) s[xb] = __builtin_fma(Pc[xb * S + y], ly, s[xb]);
+            }
+#pragma unroll
+            for (int xb = 0; xb < XB; ++xb) acc[xb] *= s[xb];
           }
+        }
 #pragma unroll
-          for (int xb = 0; xb < XB; ++xb) acc[xb] *= s[xb];
+        for (int xb = 0; xb < XB; ++xb) {
+          if (SCALE) m = fmax(m, scale_key(acc[xb], sg));
+          outp[(size_t)(c * S + x0 + xb) * kTile] = acc[xb];
         }
       }
-#pragma unroll
-      for (int xb = 0; xb < XB; ++xb) {
-        if (SCALE) m = fmax(m, scale_key(acc[xb], sg));
-        outp[(size_t)(c * S + x0 + xb) * kTile] = acc[xb];
+    }
+    if (SCALE)
+      for (; m > 0.0 && m < kScaleThr; m *= kScaleUp) {  // until back in [2^-256, 1)
+        for (int i = 0; i < CS; ++i) outp[(size_t)i * kTile] *= kScaleUp;
+        cnt += 1;
       }
-    }
-  }
-  if (SCALE) {
-    if (m > 0.0 && m < kScaleThr) {
-      for (int i = 0; i < CS; ++i) outp[(size_t)i * kTile] *= kScaleUp;
-      cnt += 1;
-    }
-    a.scale[(size_t)op.parent * a.n_pad + pidx] = cnt;
-  }
+    ka = kb;
+    kb = n;
+  } while (ka < n);  // sons [ka, kb)
+  if (SCALE) a.scale[(size_t)op.parent * a.n_pad + pidx] = cnt;
 }
 
 // ---------------------------------------------------------------------------
@@ -497,49 +521,55 @@ __global__ __launch_bounds__(256) void partials_sgpr_kernel(const KOp* __restric
       if (!op.is_tip[k]) cnt += a.scale[(size_t)op.child[k] * a.n_pad + pidx];
   }
   const bool sg = (op.flags & kOpSigned) != 0;
-  double m = 0.0;
-  for (int c = 0; c < C; ++c) {
-    double acc[S];
-    if (op.flags & 1) {
+  // (an ACCUMULATE op is checked after its second son as well: partials_generic_kernel)
+  const int k_mid = (SCALE && (op.flags & 1) && n > 2) ? 2 : n;
+  int ka = 0, kb = k_mid;
+  do {
+    double m = 0.0;
+    for (int c = 0; c < C; ++c) {
+      double acc[S];
+      if ((op.flags & 1) || ka > 0) {
 #pragma unroll
-      for (int x = 0; x < S; ++x) acc[x] = outp[(size_t)(c * S + x) * kTile];
-    } else {
-#pragma unroll
-      for (int x = 0; x < S; ++x) acc[x] = 1.0;
-    }
-    for (int k = 0; k < n; ++k) {
-      if (op.is_tip[k]) {
-        const double* t = &tipT[k * per + (c * nc + code[k]) * S];
-#pragma unroll
-        for (int x = 0; x < S; ++x) acc[x] *= t[x];
+        for (int x = 0; x < S; ++x) acc[x] = outp[(size_t)(c * S + x) * kTile];
       } else {
-        const double* L = a.partials + (size_t)op.child[k] * a.slot_stride + toff + (size_t)c * S * kTile;
-        double l[S];
 #pragma unroll
-        for (int y = 0; y < S; ++y) l[y] = __builtin_nontemporal_load(L + (size_t)y * kTile);
-        const double* __restrict__ P = pmats + ((size_t)op.branch[k] * C + c) * S * S;
+        for (int x = 0; x < S; ++x) acc[x] = 1.0;
+      }
+      for (int k = ka; k < kb; ++k) {
+        if (op.is_tip[k]) {
+          const double* t = &tipT[k * per + (c * nc + code[k]) * S];
 #pragma unroll
-        for (int x = 0; x < S; ++x) {
-          double s = P[x * S] * l[0];
+          for (int x = 0; x < S; ++x) acc[x] *= t[x];
+        } else {
+          const double* L = a.partials + (size_t)op.child[k] * a.slot_stride + toff + (size_t)c * S * kTile;
+          double l[S];
 #pragma unroll
-          for (int y = 1; y < S; ++y) s = __builtin_fma(P[x * S + y], l[y], s);
-          acc[x] *= s;
+          for (int y = 0; y < S; ++y) l[y] = __builtin_nontemporal_load(L + (size_t)y * kTile);
+          const double* __restrict__ P = pmats + ((size_t)op.branch[k] * C + c) * S * S;
+#pragma unroll
+          for (int x = 0; x < S; ++x) {
+            double s = P[x * S] * l[0];
+#pragma unroll
+            for (int y = 1; y < S; ++y) s = __builtin_fma(P[x * S + y], l[y], s);
+            acc[x] *= s;
+          }
         }
       }
-    }
 #pragma unroll
-    for (int x = 0; x < S; ++x) {
-      if (SCALE) m = fmax(m, scale_key(acc[x], sg));
-      outp[(size_t)(c * S + x) * kTile] = acc[x];
+      for (int x = 0; x < S; ++x) {
+        if (SCALE) m = fmax(m, scale_key(acc[x], sg));
+        outp[(size_t)(c * S + x) * kTile] = acc[x];
+      }
     }
-  }
-  if (SCALE) {
-    if (m > 0.0 && m < kScaleThr) {
-      for (int i = 0; i < CS; ++i) outp[(size_t)i * kTile] *= kScaleUp;
-      cnt += 1;
-    }
-    a.scale[(size_t)op.parent * a.n_pad + pidx] = cnt;
-  }
+    if (SCALE)
+      for (; m > 0.0 && m < kScaleThr; m *= kScaleUp) {  // until back in [2^-256, 1)
+        for (int i = 0; i < CS; ++i) outp[(size_t)i * kTile] *= kScaleUp;
+        cnt += 1;
+      }
+    ka = kb;
+    kb = n;
+  } while (ka < n);  // sons [ka, kb)
+  if (SCALE) a.scale[(size_t)op.parent * a.n_pad + pidx] = cnt;
 }
 
 // ---------------------------------------------------------------------------

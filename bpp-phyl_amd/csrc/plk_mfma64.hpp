@@ -54,81 +54,90 @@ __global__ __launch_bounds__(kM64Threads) void partials_mfma64_kernel(const KOp*
       if (!op.is_tip[k]) cnt += a.scale[(size_t)op.child[k] * a.n_pad + pidx];
   }
   const bool sg = (op.flags & kOpSigned) != 0;
-  double m = 0.0;
-
-  for (int c = 0; c < C; ++c) {
-    f64x4 acc[4];
-    if (op.flags & 1) {
+  // an ACCUMULATE op carries the running product as one factor already: it is checked after
+  // its second son as well (sons [0, 2), then [2, n)), so that at most three stored vectors
+  // enter the product between two checks (plk_tree4.hpp: scale_check_after).  ka, kb and n
+  // are the op's, the same for every thread of the workgroup: the barriers below stay uniform.
+  const int k_mid = (SCALE && (op.flags & 1) && n > 2) ? 2 : n;
+  int ka = 0, kb = k_mid, rs = 0;
+  do {
+    double m = 0.0;
+    for (int c = 0; c < C; ++c) {
+      f64x4 acc[4];
+      if ((op.flags & 1) || ka > 0) {
+#pragma unroll
+        for (int xt = 0; xt < 4; ++xt)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) acc[xt][r] = outp[(size_t)(c * S + 16 * xt + lr + 4 * r) * kTile];
+      } else {
+#pragma unroll
+        for (int xt = 0; xt < 4; ++xt) acc[xt] = (f64x4){1.0, 1.0, 1.0, 1.0};
+      }
+      for (int k = ka; k < kb; ++k) {
+        if (op.is_tip[k]) {
+          const int code = a.codes[(size_t)op.child[k] * a.n_pad + pidx];
+          __syncthreads();  // previous users of the LDS image are done
+          const double* src = a.tipP + ((size_t)op.child[k] * C + c) * nc * S;
+          for (int i = threadIdx.x; i < nc * S; i += kM64Threads) lds[i] = src[i];
+          __syncthreads();
+          // D[x][p] = tipP[code(p)][x]
+          const double* t = lds + code * S;
+#pragma unroll
+          for (int xt = 0; xt < 4; ++xt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc[xt][r] *= t[16 * xt + lr + 4 * r];
+        } else {
+          // the child's 64 x 16 slab of this wave: all 16 B fragments in flight first
+          const double* L = a.partials + (size_t)op.child[k] * a.slot_stride + tbase + (size_t)c * S * kTile + pw + lc;
+          double bf[16];
+#pragma unroll
+          for (int ks = 0; ks < 16; ++ks) bf[ks] = L[(size_t)(4 * ks + lr) * kTile];
+          __syncthreads();
+          const double* src = pmatsT + ((size_t)op.branch[k] * C + c) * S * S;  // P^T[y][x]
+          for (int i = threadIdx.x; i < S * S; i += kM64Threads) lds[(i >> 6) * kM64Ld + (i & 63)] = src[i];
+          __syncthreads();
+          f64x4 d[4];
+#pragma unroll
+          for (int xt = 0; xt < 4; ++xt) d[xt] = (f64x4){0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+          for (int ks = 0; ks < 16; ++ks) {
+            const int y = 4 * ks + lr;
+            double af[4];
+#pragma unroll
+            for (int xt = 0; xt < 4; ++xt) af[xt] = lds[y * kM64Ld + 16 * xt + lc];
+#pragma unroll
+            for (int xt = 0; xt < 4; ++xt) d[xt] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[xt], bf[ks], d[xt], 0, 0, 0);
+          }
+#pragma unroll
+          for (int xt = 0; xt < 4; ++xt) acc[xt] *= d[xt];
+        }
+      }
 #pragma unroll
       for (int xt = 0; xt < 4; ++xt)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) acc[xt][r] = outp[(size_t)(c * S + 16 * xt + lr + 4 * r) * kTile];
-    } else {
-#pragma unroll
-      for (int xt = 0; xt < 4; ++xt) acc[xt] = (f64x4){1.0, 1.0, 1.0, 1.0};
-    }
-    for (int k = 0; k < n; ++k) {
-      if (op.is_tip[k]) {
-        const int code = a.codes[(size_t)op.child[k] * a.n_pad + pidx];
-        __syncthreads();  // previous users of the LDS image are done
-        const double* src = a.tipP + ((size_t)op.child[k] * C + c) * nc * S;
-        for (int i = threadIdx.x; i < nc * S; i += kM64Threads) lds[i] = src[i];
-        __syncthreads();
-        // D[x][p] = tipP[code(p)][x]
-        const double* t = lds + code * S;
-#pragma unroll
-        for (int xt = 0; xt < 4; ++xt)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) acc[xt][r] *= t[16 * xt + lr + 4 * r];
-      } else {
-        // the child's 64 x 16 slab of this wave: all 16 B fragments in flight first
-        const double* L = a.partials + (size_t)op.child[k] * a.slot_stride + tbase + (size_t)c * S * kTile + pw + lc;
-        double bf[16];
-#pragma unroll
-        for (int ks = 0; ks < 16; ++ks) bf[ks] = L[(size_t)(4 * ks + lr) * kTile];
-        __syncthreads();
-        const double* src = pmatsT + ((size_t)op.branch[k] * C + c) * S * S;  // P^T[y][x]
-        for (int i = threadIdx.x; i < S * S; i += kM64Threads) lds[(i >> 6) * kM64Ld + (i & 63)] = src[i];
-        __syncthreads();
-        f64x4 d[4];
-#pragma unroll
-        for (int xt = 0; xt < 4; ++xt) d[xt] = (f64x4){0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int ks = 0; ks < 16; ++ks) {
-          const int y = 4 * ks + lr;
-          double af[4];
-#pragma unroll
-          for (int xt = 0; xt < 4; ++xt) af[xt] = lds[y * kM64Ld + 16 * xt + lc];
-#pragma unroll
-          for (int xt = 0; xt < 4; ++xt) d[xt] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[xt], bf[ks], d[xt], 0, 0, 0);
+        for (int r = 0; r < 4; ++r) {
+          if (SCALE) m = fmax(m, scale_key(acc[xt][r], sg));
+          outp[(size_t)(c * S + 16 * xt + lr + 4 * r) * kTile] = acc[xt][r];
         }
+    }
+    if (SCALE) {
+      // a pattern's 64 states are spread over the 4 lane rows (lr): combine the maxima
+      double v = m;
+      v = fmax(v, __shfl_xor(v, 16, 64));
+      v = fmax(v, __shfl_xor(v, 32, 64));
+      // until the joint maximum is back in [2^-256, 1) (three stored vectors: down to 2^-768)
+      for (; v > 0.0 && v < kScaleThr; v *= kScaleUp, ++rs) {
+        for (int c = 0; c < C; ++c)
 #pragma unroll
-        for (int xt = 0; xt < 4; ++xt) acc[xt] *= d[xt];
+          for (int xt = 0; xt < 4; ++xt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) outp[(size_t)(c * S + 16 * xt + lr + 4 * r) * kTile] *= kScaleUp;
       }
     }
-#pragma unroll
-    for (int xt = 0; xt < 4; ++xt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        if (SCALE) m = fmax(m, scale_key(acc[xt][r], sg));
-        outp[(size_t)(c * S + 16 * xt + lr + 4 * r) * kTile] = acc[xt][r];
-      }
-  }
-  if (SCALE) {
-    // a pattern's 64 states are spread over the 4 lane rows (lr): combine the maxima
-    double v = m;
-    v = fmax(v, __shfl_xor(v, 16, 64));
-    v = fmax(v, __shfl_xor(v, 32, 64));
-    const bool rs = v > 0.0 && v < kScaleThr;
-    if (rs) {
-      for (int c = 0; c < C; ++c)
-#pragma unroll
-        for (int xt = 0; xt < 4; ++xt)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) outp[(size_t)(c * S + 16 * xt + lr + 4 * r) * kTile] *= kScaleUp;
-    }
-    if (lr == 0) a.scale[(size_t)op.parent * a.n_pad + pidx] = cnt + (rs ? 1 : 0);
-  }
+    ka = kb;
+    kb = n;
+  } while (ka < n);  // sons [ka, kb)
+  if (SCALE && lr == 0) a.scale[(size_t)op.parent * a.n_pad + pidx] = cnt + rs;
 }
 
 }  // namespace plk

@@ -128,11 +128,25 @@ __device__ __forceinline__ void rescale(double (&v)[CW * 4], int& cnt, double* x
     for (int k = 0; k < nw; ++k) m = fmax(m, xmax[k * 64 + lane]);
     __syncthreads();
   }
-  if (m > 0.0 && m < kScaleThr) {
+  // until the joint maximum is back in [2^-256, 1): a product of three stored vectors can be
+  // as small as 2^-768.  Every wave holds the same m, so the trip count is workgroup-uniform.
+  while (m > 0.0 && m < kScaleThr) {
 #pragma unroll
     for (int i = 0; i < CW * 4; ++i) v[i] *= kScaleUp;
     cnt += 1;
+    m *= kScaleUp;
   }
+}
+
+// The check points inside a node under PLK_FLAG_SCALING.  The sons are taken three at a time:
+// a check follows each group and, in every group but the first, the group's second son (the
+// carried product is one factor already), so that at most three stored vectors, each with its
+// joint maximum in [2^-256, 1], enter a running product between two checks: it stays above
+// 2^-768.  The node's end is always checked.  The levelwise ops (a check after an ACCUMULATE
+// op's second son and at every op's end), the links kernels and the generated kernels check at
+// the same sons, so stored values and counts agree across the paths.
+__host__ __device__ __forceinline__ constexpr bool scale_check_after(int sons) {
+  return sons >= 3 && (sons % 3 == 0 || (sons > 3 && sons % 3 == 2));
 }
 
 template <int CW, bool SCALE>
@@ -157,6 +171,7 @@ __device__ __forceinline__ void eval_node(const TreeArgs& a, const TInstr* __res
 #pragma unroll
   for (int i = 0; i < CW * 4; ++i) acc[i] = 1.0;
   cnt = 0;
+  int ns = 0;  // sons multiplied in so far
   for (;;) {
     const TInstr in = fetch_instr(pc++);
     if (in.op == T_ASCEND) {
@@ -202,6 +217,11 @@ __device__ __forceinline__ void eval_node(const TreeArgs& a, const TInstr* __res
         if (SCALE) cnt += ccnt;
       }
     }
+    // a check inside a node of more than three sons (the program words are the same for every
+    // wave of the workgroup, so all of them reach the barriers of this check or none does);
+    // the node's end has its own check
+    ++ns;
+    if (SCALE && scale_check_after(ns) && fetch_instr(pc).op != T_ASCEND) rescale<CW>(acc, cnt, xch, nw);
   }
 }
 

@@ -169,11 +169,12 @@ __global__ __launch_bounds__(256) void cherry_table_kernel(const double* __restr
   m = fmax(m, __shfl_xor(m, 16, 64));
   m = fmax(m, __shfl_xor(m, 32, 64));
   int cnt = 0;
-  if (SCALE && m > 0.0 && m < kScaleThr) {
+  if (SCALE)
+    for (; m > 0.0 && m < kScaleThr; m *= kScaleUp) {  // until back in [2^-256, 1)
 #pragma unroll
-    for (int xt = 0; xt < XT; ++xt) acc[xt] *= kScaleUp;
-    cnt = 1;
-  }
+      for (int xt = 0; xt < XT; ++xt) acc[xt] *= kScaleUp;
+      cnt += 1;
+    }
   f64x4m d[XT];
   (void)node;
   matvec_m<S>(d, acc, PTl, lr, lc);
@@ -208,10 +209,13 @@ __device__ __forceinline__ void rescale_m(MAcc<S>& v, int& cnt, double* xch, int
     for (int k = 0; k < C; ++k) m = fmax(m, xch[(k * kTreeMGroups + g) * 16 + lc]);
     __syncthreads();
   }
-  if (m > 0.0 && m < kScaleThr) {
+  // until the joint maximum is back in [2^-256, 1) (three stored vectors: down to 2^-768);
+  // every wave of the pattern group holds the same m, and no barrier follows inside the loop
+  while (m > 0.0 && m < kScaleThr) {
 #pragma unroll
     for (int xt = 0; xt < XT; ++xt) v[xt] *= kScaleUp;
     cnt += 1;
+    m *= kScaleUp;
   }
 }
 
@@ -281,6 +285,7 @@ __device__ __forceinline__ void eval_node_m(const TreeArgs& a, const TInstr* __r
 #pragma unroll
   for (int xt = 0; xt < XT; ++xt) acc[xt] = (f64x4m){1.0, 1.0, 1.0, 1.0};
   cnt = 0;
+  int ns = 0;  // sons multiplied in so far
   for (;;) {
     const TInstr in = fetch_instr(pc++);
     if (in.op == T_ASCEND) {
@@ -318,7 +323,8 @@ __device__ __forceinline__ void eval_node_m(const TreeArgs& a, const TInstr* __r
       const double* t = reinterpret_cast<const double*>(base) + ((size_t)c * a.n_codes * a.n_codes + code) * S;
       if (a.cherry_pairs) {
         const TInstr nx = fetch_instr(pc);
-        if (nx.op == T_CHERRY) {
+        // (not where a check is due between the two: then they are taken one by one)
+        if (nx.op == T_CHERRY && !(SCALE && scale_check_after(ns + 1))) {
           // a sibling cherry follows: both rows' gathers in flight at once (their L2 / MALL
           // latencies overlap); multiplied in event order, so bitwise the same
           const uint8_t* base2 = a.cherry + (size_t)nx.a * lay.stride;
@@ -347,6 +353,9 @@ __device__ __forceinline__ void eval_node_m(const TreeArgs& a, const TInstr* __r
             cnt += base2[lay.table_bytes + code2];
           }
           ++pc;
+          ns += 2;
+          if (SCALE && scale_check_after(ns) && fetch_instr(pc).op != T_ASCEND)
+            rescale_m<S>(acc, cnt, m.xch, a.C, c, g, lr, lc);
           continue;
         }
       }
@@ -391,6 +400,12 @@ __device__ __forceinline__ void eval_node_m(const TreeArgs& a, const TInstr* __r
         if (SCALE) cnt += ccnt;
       }
     }
+    // a check inside a node of more than three sons (plk_tree4.hpp: scale_check_after; the
+    // program words are the same for every wave of the workgroup, so all of them reach the
+    // barriers of this check or none does); the node's end has its own check
+    ++ns;
+    if (SCALE && scale_check_after(ns) && fetch_instr(pc).op != T_ASCEND)
+      rescale_m<S>(acc, cnt, m.xch, a.C, c, g, lr, lc);
   }
 }
 

@@ -73,7 +73,18 @@ enum {
 /* plk_create flags */
 enum {
   PLK_FLAG_SCALING = 1u << 0,    /* exact power-of-two per-pattern rescaling (deviation,
-                                    needed where the reference underflows) */
+                                    needed where the reference underflows).  Every stored L
+                                    and U has its joint maximum over classes and states in
+                                    [2^-256, 1]: a check multiplies the vector by 2^256 until
+                                    it is, and counts the steps.  A node's sons are taken
+                                    three at a time; the running product is checked after
+                                    each group, at the node's end and, from the second group
+                                    on, after the group's second son, so at most three such
+                                    vectors enter it between two checks and it stays above
+                                    2^-768.  For PLK_OP_ACCUMULATE ops that is a check after
+                                    the op's second son and one at every op's end; every
+                                    traversal path checks at the same sons, so stored values
+                                    and counts agree across them. */
   PLK_FLAG_NONNEG_GUARD = 1u << 1 /* homogeneous root guards: drop terms <= 0
                                     (RHomogeneousTreeLikelihood.cpp:197-198,212-213);
                                     without it the NH rule clamps l<0 -> 0

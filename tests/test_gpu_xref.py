@@ -86,9 +86,9 @@ class Case:
         self.kids = [c for p, ch in et.ops if p == et.root for c in ch]
         self._ref = None
 
-    def engine(self, mode, extra=0):
+    def engine(self, mode, extra=0, expect=None):
         """An engine with P, dP, d2P of every branch, after one traversal: (engine, per-pattern
-        lnL, lnL)."""
+        lnL, lnL).  expect: the kernel path to assert where a tuning knob changes it (JIT=0)."""
         eng = engine_for(self.et, self.S, self.C, self.n, self.states, self.alph.init_table, self.rates, self.probs,
                          self.pi, self.models, model_of_node=self.mon, flags=GUARD | FLAGS[mode] | extra)
         eng.update_pmatrices(self.br, self.et.brlen[self.br], None if self.mon is None else self.mon[self.br],
@@ -96,7 +96,8 @@ class Case:
         if self.w is not None:
             eng.set_pattern_weights(self.w)
         lnl, site, _ = run_engine(eng, self.et)
-        assert eng.kernel_path() == _expected_path(self.S, self.C, mode), (eng.kernel_path(), self.S, self.C, mode)
+        want = _expected_path(self.S, self.C, mode) if expect is None else expect
+        assert eng.kernel_path() == want, (eng.kernel_path(), self.S, self.C, mode)
         return eng, site, lnl
 
     def matrices(self, eng):

@@ -10,14 +10,15 @@ which the engine never stores, come from the eigen system (xref.trial_matrices).
      map_mfma_kernel, nni_coef_mfma_kernel, and POST_VALU=1.
   G  many rescaled vectors in one product.  "The scale counts cancel and are never read" holds
      while the product of the stored vectors is a normal double; the traversal's rule (x 2^256
-     once per op when the joint maximum is below 2^-256) leaves every stored vector anywhere in
+     until the joint maximum is back above 2^-256) leaves every stored vector anywhere in
      [2^-256, 1), and an NNI coefficient build multiplies four of them on a binary tree, six at
      trifurcations, a branch term of the preorder pass four at a three-son node.  A tip code
-     whose init vector is 2^-84 in every state (exact: it costs the reference no rounding)
-     stands in for a deep subtree; three such tips make a clade at 2^-252.  Each case proves
-     from the reference's vectors, reduced by the traversal's rule (_stored; confirmed against
-     plk_get_partials), that on a quarter of the patterns the fp64 product of the factors' joint
-     maxima is below 2^-1022.
+     whose init vector is 2^-84 in every state (exact: it costs the reference no rounding; the
+     tri cases' 2^-85.3 and their second code are plain doubles, no powers of two: a uniform
+     vector still goes through P as v times a row sum) stands in for a deep subtree; three such tips make
+     a clade at 2^-252.  Each case proves from the reference's vectors, reduced by the
+     traversal's rule (_stored; confirmed against plk_get_partials), that on a quarter of the
+     patterns the fp64 product of the factors' joint maxima is below 2^-1022.
   H  per-branch models (three GTR over the rooted 20-taxon tree of BC1): per-model count
      matrices, model= per NNI move; flat and under PLK_FLAG_SCALING.
 
@@ -43,21 +44,22 @@ deriv_kernel rescales after every son; results elsewhere are bitwise what they w
 on the MI355X between the two builds: NNI scores, Newton runs and site rows on 4, 20 and 64
 states, all-branch and path derivatives and posteriors on flat and rescaled handles).
 
-A note on the lower pass.  The traversal multiplies by 2^256 once per op, so a three-son op of
-sons near 2^-256 stores its result near 2^-512, and a chain of such ops leaves the double range
-in the lower pass itself (a G tree whose every root son was a tiny clade came back with zeros in
-the root partial, lnL lost); the fused tree4 traversal multiplies the five sons of a polytomy
-before its rescale, where the levelwise ops rescale after every three.  Both need tip vectors
-of 2^-84 to show and are outside this module; the cases here stay clear of them (the tri root
-keeps a cherry and an ordinary clade; the poly case runs PLK_FLAG_LEVELWISE), and
-test_xref_cpu.test_gpu_cases_best_state_and_regime holds them there.
+A note on the lower pass.  When group G was written a check stepped by 2^256 once, and the fused
+traversals checked once per node: a three-son op of sons near 2^-256 stored its result near
+2^-512, and a chain of such ops left the double range in the lower pass itself.  The cases
+stayed clear of that (the tri root kept a cherry and an ordinary clade, the poly case ran
+PLK_FLAG_LEVELWISE only).  Now every check steps until the vector is in range and every path
+checks inside a wide node (tests/test_gpu_xref_rescale.py pins that): the tri root's other
+sons are tiny as well, the poly case also runs on the fused path, and with every stored vector
+in [2^-256, 1) the tri cases reach their regime by vectors that sit within a bit of 2^-256
+(_tree_tri); test_xref_cpu.test_gpu_cases_best_state_and_regime holds the regimes on the CPU.
 
 Measured on the MI355X (worst over the cases of a group):
   E  posteriors 8.3e-16; counts 5.7e-16; NNI delta 4.1e-17, d1 1.6e-17 weight sums, d2 2.7e-16, site rows 7.8e-16;
      Newton delta at t_opt 7.4e-16
   F  posteriors 6.7e-16 (POST_VALU=1 included); counts 9.0e-16; NNI delta 1.7e-16, d1 1.4e-15 weight sums, d2 4.0e-15, site rows 1.5e-15
-  G  derivatives 3.1e-14; posteriors 6.4e-16; counts 3.6e-16; NNI delta 1.1e-16, d1 9.7e-16 weight
-     sums, d2 3.2e-15, site rows 1.6e-15; stored partials against the rule 1.9e-15
+  G  derivatives 3.1e-14; posteriors 1.0e-15; counts 3.7e-16; NNI delta 2.8e-16, d1 5.5e-16 weight
+     sums, d2 7.8e-15, site rows 2.4e-15; stored partials against the rule 3.4e-15
   H  posteriors 6.3e-16; counts 4.5e-16; NNI delta 5.3e-16, d1 2.8e-16 weight sums, d2 1.4e-15, site
      rows 5.6e-14; Newton delta at t_opt 5.9e-16
 """
@@ -68,6 +70,7 @@ import pytest
 
 import phylo
 import plk
+import rescale_rule
 import xref
 from conftest import set_tune
 
@@ -373,10 +376,14 @@ THR = LD(2) ** -256
 UP = LD(2) ** 256
 
 
-def _tiny_alphabet(alph):
-    """A copy of the alphabet whose last code is 2^-84 in every state."""
+def _tiny_alphabet(alph, tiny=TINY, shim=None):
+    """A copy of the alphabet whose last code is 2^-84 (or tiny) in every state; with shim, the
+    code before it is shim in every state."""
     tab = np.array(alph.init_table, dtype=np.float64, copy=True)
-    tab[-1] = TINY
+    tab[-1] = tiny
+    if shim is not None:
+        assert tab.shape[0] - 2 >= alph.n_states
+        tab[-2] = shim
     return phylo.Alphabet(alph.name + "-tiny", alph.n_states, alph.chars, tab), tab.shape[0] - 1
 
 
@@ -404,15 +411,21 @@ def _tree_binary():
     return f"((({cl('s')}:0.1,{cl('o')}:0.12):0.1,{cl('u')}:0.09):0.1,{r}:0.11);"
 
 
+TINY_TRI = 2.0 ** -85.3
+
+
 def _tree_tri():
     """p = (s, o, q) and g = (p, u, v) of three sons each, g a son of the three-son root, whose
-    other sons are a cherry r of two tiny tips (2^-168: with pi and W beside it U_g stays above
-    2^-256 and is stored as it is) and a clade W of ordinary tips.  (With r and W tiny clades
-    as well the lower pass itself loses the pattern: see the note on the lower pass in the
-    module docstring.)"""
+    other sons are a cherry r of two tiny tips and a tip zz.  Every stored vector is in
+    [2^-256, 1) now, so four of them multiply to less than 2^-1022 only where each is within a
+    bit of 2^-256: the tiny code of these cases is 2^-85.3, a clade of three is at 2^-255.9,
+    L_p = 2^-767.7 is stored at 2^-255.7, and zz carries a second code, 2^-85.3 / max(pi), on the
+    patterns whose tips are all tiny, so that U_g = pi (*) q_r (*) q_zz is at 2^-255.9 as well
+    and U_p, three such factors, at 2^-255.7.  The branch terms at g and at p then multiply
+    four vectors to about 2^-1023."""
     cl = lambda n, t: _clade(n, (0.1, 0.12, 0.08, 0.05, 0.06)) + f":{t}"
     return (f"((({cl('s', 0.1)},{cl('o', 0.12)},{cl('q', 0.07)}):0.1,{cl('u', 0.09)},{cl('v', 0.11)}):0.1,"
-            f"(ra:0.1,rb:0.12):0.11,{cl('W', 0.08)});")
+            f"(ra:0.1,rb:0.12):0.11,zz:0.08);")
 
 
 def _tree_poly():
@@ -430,19 +443,24 @@ G_CASES = {
     "tri-C8": (_tree_tri, True, 4, 8, 200, 14, 0.6, 0.7, "materialize"),
     "tri-S20": (_tree_tri, True, 20, 2, 200, 15, 0.6, 0.7, "materialize"),
     "poly-C4": (_tree_poly, True, 4, 4, 300, 16, 0.6, 0.7, "levelwise"),
+    "poly-C4-fused": (_tree_poly, True, 4, 4, 300, 16, 0.6, 0.7, "materialize"),
 }
 
 
-@functools.lru_cache(maxsize=None)
-def _case_g(name):
-    tree, unroot, S, C, n, seed, whole, cells, _ = G_CASES[name]
-    et = phylo.engine_tree(phylo.Tree.from_newick(tree()), unroot=unroot)
+def _tiny_case(newick, unroot, S, C, n, seed, whole, cells, alpha=0.6, tiny=TINY, shim=False):
+    """A case whose tips named by one lower-case letter and a, b or c (_clade) carry the tiny
+    code: on a share `whole` of the patterns all of them, elsewhere a share `cells` of the cells.
+    shim: the tip zz carries the code before it, tiny / max(pi) in every state, on the patterns
+    of the first kind."""
+    et = phylo.engine_tree(phylo.Tree.from_newick(newick), unroot=unroot)
     if S == 4:   # close to Jukes-Cantor (distinct eigenvalues): see _tree_binary
         m, alph = phylo.gtr(1.02, 0.98, 1.0, 1.01, 0.99, 0.2505, 0.2495, 0.25, 0.25), phylo.DNA
-    else:
+    elif S == 20:
         m, alph = phylo.lg08(), phylo.PROTEIN
-    alph, code = _tiny_alphabet(alph)
-    case = Case(et, [m], None, alph, C, n, seed=seed, alpha=200.0 if tree is _tree_binary else 0.6)
+    else:
+        m, alph = phylo.yn98(2.0, 0.3), phylo.CODON
+    alph, code = _tiny_alphabet(alph, tiny, tiny / m.pi.max() if shim else None)
+    case = Case(et, [m], None, alph, C, n, seed=seed, alpha=alpha)
     rng = np.random.default_rng(seed)
     tiny_tips = [i for i, nm in enumerate(et.tip_names) if len(nm) == 2 and nm[0].islower() and nm[1] in "abc"]
     assert len(tiny_tips) >= 12
@@ -452,48 +470,32 @@ def _case_g(name):
     rest = np.flatnonzero(~all_tiny)
     mask[np.ix_(tiny_tips, rest)] = rng.random((len(tiny_tips), len(rest))) < cells
     case.states[mask] = code
+    if shim:
+        case.states[et.tip_names.index("zz"), all_tiny] = code - 1
     case.w = rng.integers(1, 9, n).astype(np.float64)
     return case
 
 
+@functools.lru_cache(maxsize=None)
+def _case_g(name):
+    tree, unroot, S, C, n, seed, whole, cells, _ = G_CASES[name]
+    tri = tree is _tree_tri
+    return _tiny_case(tree(), unroot, S, C, n, seed, whole, cells, alpha=200.0 if tree is _tree_binary else 0.6,
+                      tiny=TINY_TRI if tri else TINY, shim=tri)
+
+
 def _stored(case, P, low):
-    """The vectors as the engine stores them under PLK_FLAG_SCALING, from the reference's own:
-    an op of at most three sons multiplies the sons' stored q and then multiplies by 2^256 once
-    where the joint maximum over classes and states is positive and below 2^-256 (a polytomy:
-    after every three sons, on the running product); the stored U of a node is the father side
-    of its branch formed from the stored vectors, rescaled once by the same rule (pi sits in
-    the root sons' U).  Returns the joint maxima per pattern, {v: [n]} for L and for U, and the
-    stored L themselves."""
+    """The vectors as the engine stores them under PLK_FLAG_SCALING (tests/rescale_rule.py:
+    stored_new, every check stepping by 2^256 until the joint maximum over classes and states is
+    back in [2^-256, 1)): the scale counts come from the fp64 walk, the vectors are the
+    reference's own times 2^(256 k).  Returns the joint maxima per pattern, {v: [n]} for L and
+    for the stored U of the internal nodes, and the stored L themselves."""
     et = case.et
-    P = xref._ld(P)
+    st = rescale_rule.stored_new(et, case.states, case.alph.init_table, P, case.pi)
     L, _ = low
-    n, C, S = case.n, case.C, case.S
-    pi = xref._ld(case.pi)
-
-    def rescaled(a):
-        m = a.max(axis=(1, 2))
-        r = (m > 0) & (m < THR)
-        a = a.copy()
-        a[r] *= UP
-        return a
-
-    Ls = {t: L[t] for t in range(et.n_tips)}
-    qs = {}
-    for p, ch in et.ops:
-        run = np.ones((n, C, S), dtype=LD)
-        for k in range(0, len(ch), 3):
-            for c in ch[k:k + 3]:
-                qs[c] = xref._apply(P[c], Ls[c])
-                run = run * qs[c]
-            run = rescaled(run)
-        Ls[p] = run
-    Us = {}
-    for p, ch in reversed(et.ops):
-        above = np.broadcast_to(pi[None, None, :], (n, C, S)) if p == et.root else xref._apply_t(P[p], Us[p])
-        for c in ch:
-            Us[c] = rescaled(above * xref._prod([qs[o] for o in ch if o != c], n, C, S))
-    mx = lambda d: {v: a.max(axis=(1, 2)).astype(np.float64) for v, a in d.items()}
-    return mx(Ls), mx(Us), Ls
+    Ls = {v: rescale_rule.scaled_reference(L[v], st.k[v]) for v in range(et.n_nodes)}
+    Lmax = {v: a.max(axis=(1, 2)).astype(np.float64) for v, a in Ls.items()}
+    return Lmax, st.Umax, Ls
 
 
 def _regime(case, Lmax, Umax):

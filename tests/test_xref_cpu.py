@@ -524,7 +524,7 @@ def _gpu_cases():
 
 
 @pytest.mark.parametrize("group", ["E C=3", "E C=8", "F S=20", "F S=64", "H flat", "H scaled", "G binary-C4", "G binary-C8",
-                                   "G poly-C4", "G tri-C4", "G tri-C8", "G tri-S20"])
+                                   "G poly-C4", "G poly-C4-fused", "G tri-C4", "G tri-C8", "G tri-S20"])
 def test_gpu_cases_best_state_and_regime(group):
     """The seeds of tests/test_gpu_xref_consumers.py: the reference alone leaves at most 1 % of the
     best_state cells inside the 1e-8 gap; the group G cases reach their regime (the product of
@@ -550,3 +550,74 @@ def test_gpu_cases_best_state_and_regime(group):
     for v in range(case.et.n_tips, case.et.n_nodes):
         m = Ls[v].max(axis=(1, 2))
         assert np.all((m == 0) | (m >= LD(2) ** -1022)), v
+
+
+# ---------------------------------------------------------------- the rescaling rule restated (tests/rescale_rule.py)
+
+def test_rescale_rule_check_points():
+    """Once per node, after every three sons, and the rule whose running products never hold more
+    than three stored vectors between two checks."""
+    import rescale_rule as rr
+    assert rr.check_points(9, False, True) == {9} and rr.check_points(9, False, False) == {3, 6, 9}
+    assert rr.check_points(5, False, False) == {3, 5} and rr.check_points(5, True) == {3, 5}
+    assert rr.check_points(9, True) == {3, 5, 6, 8, 9} and rr.check_points(10, True) == {3, 5, 6, 8, 9, 10}
+    for n in range(1, 4):
+        assert rr.check_points(n, True) == rr.check_points(n, False, True) == rr.check_points(n, False, False) == {n}
+    for n in range(1, 20):   # at most three factors between two checks: the carried product and two sons, or three sons
+        pts = sorted(rr.check_points(n, True))
+        assert pts[0] <= 3 and all(b - a <= 2 for a, b in zip(pts, pts[1:])) and pts[-1] == n
+
+
+RESCALE_CASES = ["I-C1", "I-C4", "I-C8", "I-S20", "I-S64", "J5-C1", "J5-C4", "J5-S20", "J5-S64", "J9-C4", "J9-C8", "J9-S20",
+                 "Js-C4", "Js-C8", "Js-S20", "K-C1", "K-C4", "K-S20"]
+
+
+@pytest.mark.parametrize("name", RESCALE_CASES)
+def test_rescale_cases_regime(name):
+    """The cases of tests/test_gpu_xref_rescale.py, as conditions on their inputs.  Under the
+    rule up to now (one step per check), on the check points of the path the case targets, at
+    least a quarter of the patterns end with an all-zero root partial: the fused and the
+    levelwise points alike for I, J9 and Js (Js: an all-zero U of some node as well); the fused
+    ones for J5 and K, where a check after every three sons still kept the product alive; on
+    K-C1 and K-S20 every pattern.  Under the new rule no running product's joint maximum falls
+    below 2^-1022 and every stored joint maximum lies in [2^-256, 1].  The reference's smallest
+    likelihood is far inside its range, and where the GPU tests compare best_state at most 1 %
+    of its cells lie inside the 1e-8 gap."""
+    import rescale_rule as rr
+    import test_gpu_xref_rescale as resc
+    assert sorted(RESCALE_CASES) == sorted(resc.CASES)
+    case = resc.case_of(name)
+    et = case.et
+    tree = resc.CASES[name][0]
+    assert max(len(ch) for _, ch in et.ops) == {"i": 3, "root5": 5, "root9": 9, "son": 9, "star": et.n_tips}[tree]
+    P = _eigen_P(case)
+    args = (et, case.states, case.alph.init_table, P, case.pi)
+    x = xref.updown(*args[:4], None, None, case.probs, case.pi)
+    assert x.l.min() > xref.RANGE_MIN
+    if tree in ("i", "son"):
+        top = np.sort(xref.posteriors(*args[:4], case.probs, case.pi, _internal(et)).states, axis=2)
+        assert 1.0 - float(np.asarray(top[:, :, -1] - top[:, :, -2] > 1e-8).mean()) <= 0.01
+    shares = {}
+    for fused in (True, False):
+        old = rr.stored_once(*args, fused)
+        shares[fused] = (float(rr.lost_lower(old, et).mean()), float(rr.lost_upper(old).mean()) if old.U else 0.0)
+    assert shares[True][0] >= (1.0 if name in ("K-C1", "K-S20") else 0.25), shares
+    if tree in ("i", "root9", "son"):
+        assert shares[False][0] >= 0.25, shares
+    if tree == "son":
+        assert shares[True][1] >= 0.25 and shares[False][1] >= 0.25, shares
+    new = rr.stored_new(*args)
+    steps = max(int((new.k[p] - sum(new.k[c] for c in ch)).max()) for p, ch in et.ops)
+    print(f"{name}: root partial all zero under one step per check on {shares[True][0]:.0%} of the patterns (fused), "
+          f"{shares[False][0]:.0%} (levelwise), some stored U on {shares[True][1]:.0%}; new rule: smallest running maximum "
+          f"2^{float(np.log2(new.low.min())):.0f}, most steps in one node {steps}; smallest likelihood "
+          f"2^{float(np.log2(x.l.min())):.0f}")
+    assert new.low.min() >= rr.NORMAL_MIN
+    assert rr.in_range(new, et)
+    assert not rr.lost_lower(new, et).any() and not (new.U and rr.lost_upper(new).any())
+    assert steps >= 2
+    # the counts are those of the reference's own magnitudes: L_ref 2^(256 k) has its joint maximum in [2^-256, 1)
+    L, _ = xref.lower(*args[:4])
+    for v in range(et.n_tips, et.n_nodes):
+        m = rr.scaled_reference(L[v], new.k[v]).max(axis=(1, 2))
+        assert np.all((m >= LD(2) ** -256) & (m < 1)), v
