@@ -19,6 +19,7 @@
 #include "plk_rell.hpp"
 #include "plk_pair.hpp"
 #include "plk_pars.hpp"
+#include "plk_sim.hpp"
 #include "plk_exchange.hpp"
 
 #include <hip/hip_runtime.h>
@@ -37,6 +38,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <set>
 #include <thread>
 #include <cstdarg>
 #include <cstdlib>
@@ -448,6 +450,14 @@ struct plk_handle_s {
   int pars_root = -1;                   // -1: no plk_pars_update yet
   uint64_t pars_total = 0;              // its weighted score
   int64_t pars_launches = 0;            // kernel launches of the last parsimony call
+  // simulation (plk_sim.hpp): the states of the last plk_simulate and its tree
+  uint8_t* sim_states = nullptr;        // [n_nodes + 1][n_pad] state per site and node; the last row the classes
+  size_t sim_states_cap = 0;
+  char* d_sim = nullptr;                // cumulative rows, fallback indices, the preorder list, the code of each state
+  size_t d_sim_cap = 0;
+  std::vector<int> sim_parent;          // father per node of that tree (-1: the root, or outside the tree)
+  int sim_root = -1;                    // -1: no plk_simulate yet
+  int64_t sim_launches = 0;             // kernel launches of the last plk_simulate
   // RELL resampling (plk_rell.hpp): site rows [rell_n_rows][n_pad] and replicate weights
   // [rell_R][n_pad], padding 0.0; a multi-device parent keeps the two counts only
   double* rell_rows = nullptr;
@@ -1262,7 +1272,7 @@ int plk_destroy(plk_handle h) {
                   h->d_cherry_rows, h->d_kidsl, h->d_cls, h->d_ucodes_dc, h->d_units_start, h->d_post, h->post_buf,
                   h->count_G, h->wmats, h->d_mapb, h->map_blk, h->d_mapreq, h->d_nni, h->nni_vit, h->d_pair,
                   h->rell_rows, h->rell_W, h->rell_stage, h->rell_bad, h->pars_sets, h->pars_scores, h->d_pars,
-                  h->d_pars_moves};
+                  h->d_pars_moves, h->sim_states, h->d_sim};
   for (void* p : bufs)
     if (p) hipFree(p);
   if (h->h_req) (void)hipHostFree(h->h_req);
@@ -6136,6 +6146,226 @@ int plk_pars_nni_scores(plk_handle h, int n_moves, const int32_t* son, const int
 int plk_pars_launches(plk_handle h, int64_t* launches) {
   if (!h || !launches) return fail(h, PLK_ERR_ARG, "null argument");
   *launches = h->pars_launches;
+  return PLK_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Simulation (plk_sim.hpp): one table build and one walk down the tree per call.
+// ---------------------------------------------------------------------------
+int plk_simulate(plk_handle h, const plk_op* ops, int n_ops, int root, uint64_t seed, uint64_t replicate,
+                 int64_t site0, const uint8_t* state_code, unsigned flags) {
+  env_refresh();
+  if (h && !h->shards.empty())
+    return multi_slices(h, [&](plk_handle x, int64_t a) {
+      return plk_simulate(x, ops, n_ops, root, seed, replicate, site0 + a, state_code, flags);
+    });
+  if (!h) return fail(nullptr, PLK_ERR_ARG, "null handle");
+  if (!ops || n_ops <= 0) return fail(h, PLK_ERR_ARG, "empty op list");
+  if (flags & ~(unsigned)PLK_SIM_SET_TIPS) return fail(h, PLK_ERR_ARG, "unknown flags 0x%x", flags);
+  if (site0 < 0) return fail(h, PLK_ERR_ARG, "negative site0");
+  const int nt = h->n_tips, nn = h->n_nodes, S = h->S, C = h->C;
+  const bool set_tips = (flags & PLK_SIM_SET_TIPS) != 0;
+  std::vector<std::vector<int> > kids((size_t)nn);
+  std::vector<int> parent((size_t)nn, -1), order;
+  std::vector<char> done((size_t)nn, 0);
+  for (int i = 0; i < n_ops; ++i) {
+    const plk_op& o = ops[i];
+    if (o.parent < nt || o.parent >= nn) return fail(h, PLK_ERR_ARG, "op %d: parent %d is not an internal node", i, o.parent);
+    if (o.n_children < 1 || o.n_children > 3) return fail(h, PLK_ERR_ARG, "op %d: %d children", i, o.n_children);
+    if (o.flags & PLK_OP_ACCUMULATE) {
+      if (!done[o.parent]) return fail(h, PLK_ERR_ARG, "op %d: accumulate into node %d that no earlier op formed", i, o.parent);
+    } else {
+      if (done[o.parent]) return fail(h, PLK_ERR_ARG, "op %d: node %d formed twice", i, o.parent);
+      order.push_back(o.parent);
+    }
+    for (int k = 0; k < o.n_children; ++k) {
+      const int c = o.child[k];
+      if (c < 0 || c >= nn || c == o.parent) return fail(h, PLK_ERR_ARG, "op %d: bad child %d", i, c);
+      if (c >= nt && !done[c]) return fail(h, PLK_ERR_ARG, "op %d: node %d is formed by no earlier op (postorder)", i, c);
+      if (parent[c] >= 0) return fail(h, PLK_ERR_ARG, "op %d: node %d has two fathers", i, c);
+      parent[c] = o.parent;
+      kids[o.parent].push_back(c);
+    }
+    done[o.parent] = 1;
+  }
+  if (ops[n_ops - 1].parent != root) return fail(h, PLK_ERR_ARG, "the last op's parent %d is not the root %d", ops[n_ops - 1].parent, root);
+  if (parent[root] >= 0) return fail(h, PLK_ERR_ARG, "the root %d has a father", root);
+  for (int v : order)
+    if (v != root && parent[v] < 0) return fail(h, PLK_ERR_ARG, "node %d does not hang below the root %d", v, root);
+  // The walk's list: fathers first, and nodes whose draw indices share a Philox block (k >> 2,
+  // k = 2 + node) next to each other where the tree allows, since a lane keeps its last block.
+  // Among the nodes whose father is listed: one of the current block; else the highest internal
+  // node (the reverse of a postorder numbering: consecutive indices), and the tips, lowest first,
+  // once no internal node is left.  The order changes no draw.
+  const TopoView tv(kids, root);
+  std::vector<int2> list;
+  {
+    std::set<int> ready[2];  // internal nodes, tips
+    auto release = [&](int v) {
+      for (int c : tv.kids[v]) ready[c < nt].insert(c);
+    };
+    auto of_block = [&](std::set<int>& r, int blk) {
+      auto it = r.lower_bound(4 * blk - 2);
+      return it != r.end() && ((*it + 2) >> 2) == blk ? *it : -1;
+    };
+    release(root);
+    int blk = 0;  // the root state is draw 1
+    while (!ready[0].empty() || !ready[1].empty()) {
+      int v = of_block(ready[0], blk);
+      if (v < 0) v = of_block(ready[1], blk);
+      if (v < 0) v = !ready[0].empty() ? *ready[0].rbegin() : *ready[1].begin();
+      ready[v < nt].erase(v);
+      list.push_back(make_int2(v, tv.parent[v]));
+      blk = (v + 2) >> 2;
+      release(v);
+    }
+  }
+  for (const int2& e : list)
+    if (!h->pmat_valid[e.x]) return fail(h, PLK_ERR_STATE, "branch %d has no transition matrix", e.x);
+  if (!h->rates_set) return fail(h, PLK_ERR_STATE, "category rates not set");
+  if (!h->pi_set) return fail(h, PLK_ERR_STATE, "root frequencies not set");
+  uint8_t code_of_state[64] = {0};
+  if (set_tips) {
+    if (!h->table_set) return fail(h, PLK_ERR_STATE, "plk_set_code_table must precede plk_simulate with PLK_SIM_SET_TIPS");
+    bool seen[256] = {false};
+    for (int s = 0; s < S; ++s) {
+      const int c = state_code ? state_code[s] : s;
+      if (c >= h->n_codes_table)
+        return fail(h, PLK_ERR_ARG, "state %d: code %d outside the code table (%d codes)", s, c, h->n_codes_table);
+      seen[c] = true;
+    }
+    bool grown = false;
+    for (int c = 0; c < 256; ++c)
+      if (seen[c] && h->code_map[c] < 0) {
+        h->code_map[c] = (int)h->code_orig.size();
+        h->code_orig.push_back(c);
+        grown = true;
+      }
+    if (grown) {
+      int rc = upload_compact_table(h);
+      if (rc) return rc;
+    }
+    for (int s = 0; s < S; ++s) code_of_state[s] = (uint8_t)h->code_map[state_code ? state_code[s] : s];
+  }
+
+  hipSetDevice(h->device);
+  h->sim_root = -1;
+  const size_t n_rows = (size_t)nn * C * S;
+  const size_t off_cls = n_rows * S * sizeof(double), off_root = off_cls + 17 * sizeof(double);
+  const size_t off_fb = off_root + 65 * sizeof(double);
+  const size_t off_list = (off_fb + n_rows * sizeof(int32_t) + 7) & ~(size_t)7;
+  const size_t off_code = off_list + std::max<size_t>(list.size(), 1) * sizeof(int2);
+  int rc;
+  if ((rc = ensure_cap(h, (void**)&h->d_sim, &h->d_sim_cap, off_code + 64))) return rc;
+  if ((rc = ensure_cap(h, (void**)&h->sim_states, &h->sim_states_cap, (size_t)(nn + 1) * h->n_pad))) return rc;
+  if (!list.empty())
+    HIPCHK(h, hipMemcpyAsync(h->d_sim + off_list, list.data(), list.size() * sizeof(int2), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(h->d_sim + off_code, code_of_state, 64, hipMemcpyHostToDevice, h->stream));
+  SimArgs a;
+  a.pmats = h->pmats;
+  a.probs = h->probs;
+  a.pi = h->pi;
+  a.cdf = reinterpret_cast<double*>(h->d_sim);
+  a.cdf_cls = reinterpret_cast<double*>(h->d_sim + off_cls);
+  a.cdf_root = reinterpret_cast<double*>(h->d_sim + off_root);
+  a.fb = reinterpret_cast<int32_t*>(h->d_sim + off_fb);
+  a.list = reinterpret_cast<const int2*>(h->d_sim + off_list);
+  a.n_list = (int32_t)list.size();
+  a.S = S;
+  a.C = C;
+  a.root = root;
+  a.n_tips = nt;
+  a.states = h->sim_states;
+  a.n_nodes = nn;
+  a.codes = set_tips ? h->codes : nullptr;
+  a.code_of_state = reinterpret_cast<const uint8_t*>(h->d_sim + off_code);
+  a.n_pad = h->n_pad;
+  a.n_patterns = h->n_patterns;
+  a.seed = seed;
+  a.replicate = replicate;
+  a.site0 = (uint64_t)site0;
+  const unsigned cdf_blocks = (unsigned)((list.size() * C * S + 2 + kSimThreads - 1) / kSimThreads);
+  const unsigned walk_blocks = (unsigned)((h->n_patterns + kSimThreads - 1) / kSimThreads);
+  {  // with plk_set_timing: the table build is timed as PLK_TIME_TABLES, the walk as PLK_TIME_PARTIALS
+    TimedSpan span(h, PLK_TIME_TABLES, 3);
+    sim_cdf_kernel<<<cdf_blocks, kSimThreads, 0, h->stream>>>(a);
+    HIPCHK(h, hipGetLastError());
+    if (span.stop()) h->n_table_launches++;
+  }
+  {
+    TimedSpan span(h, PLK_TIME_PARTIALS, 0);
+    // 4 states: the tables in LDS where two workgroups' copies fit a CU (PLK_TUNE SIM_LDS=0: never)
+    const size_t lds = n_rows * (S * sizeof(double) + sizeof(int32_t));
+    if (S == 4 && lds <= kSimLdsMax && !tune_is("SIM_LDS", '0')) {
+      const unsigned lds_blocks = (unsigned)((h->n_patterns + kSimLdsThreads - 1) / kSimLdsThreads);
+      sim_walk_kernel<4, true><<<lds_blocks, kSimLdsThreads, lds, h->stream>>>(a);
+    } else if (S == 4)
+      sim_walk_kernel<4, false><<<walk_blocks, kSimThreads, 0, h->stream>>>(a);
+    else if (S == 20)
+      sim_walk_kernel<20, false><<<walk_blocks, kSimThreads, 0, h->stream>>>(a);
+    else if (S == 64)
+      sim_walk_kernel<64, false><<<walk_blocks, kSimThreads, 0, h->stream>>>(a);
+    else
+      sim_walk_kernel<0, false><<<walk_blocks, kSimThreads, 0, h->stream>>>(a);
+    HIPCHK(h, hipGetLastError());
+    if (span.stop()) h->n_launches++;
+  }
+  h->sim_launches = 2;
+  if (set_tips) {
+    // what plk_set_tip_codes invalidates, for every tip at once
+    for (const int2& e : list)
+      if (e.x < nt) h->tip_set[e.x] = 1;
+    h->state_epoch++;
+    h->pars_root = -1;
+    h->ucodes_valid = false;
+    h->cherry_codes_valid = false;
+    h->fused_lnl_valid = false;
+    h->cmp_valid = false;
+    if (h->flags & PLK_FLAG_SUBTREE_PATTERNS) {  // the link build reads the codes on the host
+      if (h->tip_codes_host.empty()) h->tip_codes_host.resize(nt);
+      for (const int2& e : list)
+        if (e.x < nt) {
+          h->tip_codes_host[e.x].resize((size_t)h->n_patterns);
+          HIPCHK(h, hipMemcpyAsync(h->tip_codes_host[e.x].data(), h->codes + (size_t)e.x * h->n_pad, (size_t)h->n_patterns,
+                                   hipMemcpyDeviceToHost, h->stream));
+        }
+    }
+  }
+  HIPCHK(h, hipStreamSynchronize(h->stream));  // the list and the codes are locals
+  h->sim_parent.swap(parent);
+  h->sim_root = root;
+  return PLK_OK;
+}
+
+static int sim_get_row(plk_handle h, int row, uint8_t* out) {
+  hipSetDevice(h->device);
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, hipMemcpy(out, h->sim_states + (size_t)row * h->n_pad, (size_t)h->n_patterns, hipMemcpyDeviceToHost));
+  return PLK_OK;
+}
+
+int plk_sim_get_states(plk_handle h, int node, uint8_t* states) {
+  env_refresh();
+  if (!h || !states) return fail(h, PLK_ERR_ARG, "null argument");
+  if (!h->shards.empty()) return multi_slices(h, [&](plk_handle x, int64_t a) { return plk_sim_get_states(x, node, states + a); });
+  if (h->sim_root < 0) return fail(h, PLK_ERR_STATE, "no plk_simulate yet");
+  if (node < 0 || node >= h->n_nodes || (node != h->sim_root && h->sim_parent[(size_t)node] < 0))
+    return fail(h, PLK_ERR_ARG, "node %d is not in the simulated tree", node);
+  return sim_get_row(h, node, states);
+}
+
+int plk_sim_get_classes(plk_handle h, uint8_t* classes) {
+  env_refresh();
+  if (!h || !classes) return fail(h, PLK_ERR_ARG, "null argument");
+  if (!h->shards.empty()) return multi_slices(h, [&](plk_handle x, int64_t a) { return plk_sim_get_classes(x, classes + a); });
+  if (h->sim_root < 0) return fail(h, PLK_ERR_STATE, "no plk_simulate yet");
+  return sim_get_row(h, h->n_nodes, classes);
+}
+
+int plk_sim_launches(plk_handle h, int64_t* launches) {
+  if (!h || !launches) return fail(h, PLK_ERR_ARG, "null argument");
+  if (!h->shards.empty()) return plk_sim_launches(h->shards[0], launches);
+  *launches = h->sim_launches;
   return PLK_OK;
 }
 

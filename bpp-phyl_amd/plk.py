@@ -27,6 +27,7 @@ PLK_FLAG_DOUBLE_RECURSIVE = 32
 PLK_DERIV_P, PLK_DERIV_DP, PLK_DERIV_D2P = 1, 2, 4
 PLK_OP_ACCUMULATE = 1
 PLK_TIME_PARTIALS, PLK_TIME_PMAT, PLK_TIME_ROOT, PLK_TIME_TABLES = 1, 2, 4, 8
+PLK_SIM_SET_TIPS = 1
 
 # every symbol include/plk.h declares
 EXPORTS = [
@@ -45,7 +46,8 @@ EXPORTS = [
     "plk_pair_distances", "plk_pair_passes", "plk_site_rows_reserve", "plk_site_row_set", "plk_site_row_get",
     "plk_site_row_from_root", "plk_nni_site_rows", "plk_set_replicate_weights", "plk_replicate_sums",
     "plk_replicate_passes", "plk_pars_set_code_masks", "plk_pars_update", "plk_pars_score", "plk_pars_get_edge",
-    "plk_pars_nni_scores", "plk_pars_launches",
+    "plk_pars_nni_scores", "plk_pars_launches", "plk_simulate", "plk_sim_get_states", "plk_sim_get_classes",
+    "plk_sim_launches",
 ]
 
 
@@ -161,6 +163,11 @@ def load(path: str = LIB_PATH) -> ct.CDLL:
         "plk_pars_get_edge": ([ct.c_void_p, ct.c_int, ct.c_int, P(ct.c_uint64), P(ct.c_uint32)], ct.c_int),
         "plk_pars_nni_scores": ([ct.c_void_p, ct.c_int, ip, ip, P(ct.c_int64)], ct.c_int),
         "plk_pars_launches": ([ct.c_void_p, P(ct.c_int64)], ct.c_int),
+        "plk_simulate": ([ct.c_void_p, P(plk_op), ct.c_int, ct.c_int, ct.c_uint64, ct.c_uint64, ct.c_int64,
+                          P(ct.c_uint8), ct.c_uint], ct.c_int),
+        "plk_sim_get_states": ([ct.c_void_p, ct.c_int, P(ct.c_uint8)], ct.c_int),
+        "plk_sim_get_classes": ([ct.c_void_p, P(ct.c_uint8)], ct.c_int),
+        "plk_sim_launches": ([ct.c_void_p, P(ct.c_int64)], ct.c_int),
         "plk_kernel_path": ([ct.c_void_p], ct.c_char_p),
         "plk_compressed_work": ([ct.c_void_p, P(ct.c_int64)], ct.c_int),
         "plk_evaluate": ([ct.c_void_p, ct.c_int, ip, ip, dp, P(plk_op), ct.c_int, ct.c_int, dp, dp], ct.c_int),
@@ -750,6 +757,41 @@ class Engine:
     def pars_launches(self) -> int:
         n = ct.c_int64(0)
         self._chk(self.lib.plk_pars_launches(self.h, ct.byref(n)))
+        return n.value
+
+    # Simulation: counter-based draws down the tree, tip codes written where the traversals read them
+
+    def simulate(self, ops: Sequence[Tuple[int, Sequence[int], int]], root: int, seed: int, replicate: int = 0,
+                 site0: int = 0, state_code=None, set_tips: bool = True):
+        """plk_simulate: a rate class per site and a state per site and node of the tree `ops`
+        (postorder, the last op's parent `root`), a pure function of (seed, replicate, site0 + site,
+        node).  set_tips stores the tips' states as tip codes (state s as state_code[s]; None: as
+        code s), as set_tip_codes of every tip would."""
+        arr = self._op_array(ops)
+        sp = None
+        if state_code is not None:
+            sc = np.ascontiguousarray(state_code, dtype=np.uint8).ravel()
+            if len(sc) != self.S:
+                raise ValueError("state_code has one entry per state")
+            sp = sc.ctypes.data_as(ct.POINTER(ct.c_uint8))
+        self._chk(self.lib.plk_simulate(self.h, arr, len(arr), int(root), int(seed), int(replicate), int(site0), sp,
+                                        PLK_SIM_SET_TIPS if set_tips else 0))
+
+    def sim_states(self, node: int) -> np.ndarray:
+        """plk_sim_get_states: the state index of `node` at every site of the last simulate (uint8)."""
+        out = np.empty(self.P, dtype=np.uint8)
+        self._chk(self.lib.plk_sim_get_states(self.h, int(node), out.ctypes.data_as(ct.POINTER(ct.c_uint8))))
+        return out
+
+    def sim_classes(self) -> np.ndarray:
+        """plk_sim_get_classes: the rate class of every site of the last simulate (uint8)."""
+        out = np.empty(self.P, dtype=np.uint8)
+        self._chk(self.lib.plk_sim_get_classes(self.h, out.ctypes.data_as(ct.POINTER(ct.c_uint8))))
+        return out
+
+    def sim_launches(self) -> int:
+        n = ct.c_int64(0)
+        self._chk(self.lib.plk_sim_launches(self.h, ct.byref(n)))
         return n.value
 
     def set_timing(self, on: bool):

@@ -56,8 +56,8 @@ extern "C" {
 #endif
 
 /* 2: plk_timing gained `evaluations` and `host_us` (a caller built against 1 must not pass
- * its smaller struct to plk_get_timing_ex).  Added entry points (the plk_pars_* calls last)
- * change no struct or signature and leave the version as it is. */
+ * its smaller struct to plk_get_timing_ex).  Added entry points (the plk_pars_* calls, then
+ * plk_simulate and plk_sim_*) change no struct or signature and leave the version as it is. */
 #define PLK_ABI_VERSION 2
 
 enum {
@@ -676,6 +676,65 @@ int plk_pars_nni_scores(plk_handle h, int n_moves, const int32_t* son, const int
 /* Kernel launches of the last plk_pars_update or plk_pars_nni_scores on this handle.
  * Every parsimony call: PLK_ERR_STATE before plk_pars_update (where it reads its tree). */
 int plk_pars_launches(plk_handle h, int64_t* launches);
+
+/* Simulation of an alignment under the handle's model: per site a rate class, a root state and,
+ * down the tree, a state per node.  Replaces NonHomogeneousSequenceSimulator::simulate
+ * (Simulation/NonHomogeneousSequenceSimulator.cpp: the cumulative tables of the constructor,
+ * :110-160, the per-site walk, :306-353, and the draw, :433-483) and the host pass and copy of
+ * plk_set_tip_codes that would follow it: the tip codes are written where the next traversal
+ * reads them.
+ *
+ * The draw is a pure function of (seed, replicate, global site index, node); it depends neither
+ * on the launch geometry, nor on sharding, nor on the order in which the ops describe the tree.
+ *   Generator: Philox4x64-10 (Salmon et al. 2011), multipliers 0xD2E7470EE14C6C93 and
+ *     0xCA5A826395121157, key increments 0x9E3779B97F4A7C15 and 0xBB67AE8584CAA73B; per round,
+ *     with hi/lo of the products M0 c0 and M1 c2,  c = [hi1^c1^k0, lo1, hi0^c3^k1, lo0], the key
+ *     incremented between rounds.  Counter 0, key 0 gives 16554d9eca36314c db20fe9d672d0fdc
+ *     d7e772cee186176b 7e68b68aec7ba23b.
+ *   Uniform number: u(site, k) = (w >> 11) * 2^-53 in [0, 1), w the word k & 3 of
+ *     Philox(counter = (site, k >> 2, replicate, 0), key = (seed, 0)), site = site0 + the local
+ *     index.
+ *   Draw index k: 0 the site's rate class, 1 the root state, 2 + v the state of node v, for every
+ *     node v of the tree other than the root.
+ *   Inverse CDF: for a probability row p[0 .. n) the cumulative sums are sequential in fp64
+ *     (cum[0] = p[0], cum[y] = cum[y-1] + p[y]); the drawn index is the first y with u < cum[y]
+ *     (the reference's rule, :433-440) and, where there is none (rounding, a row that does not sum
+ *     to 1), the largest y with p[y] > 0 (0 for a row without one).  Rows are expected
+ *     non-negative.
+ *   Rows: the class row is the class probabilities of plk_set_category_rates (the reference draws
+ *     the class uniformly, which is the same thing for the equiprobable classes of a discretised
+ *     gamma law); the root row is plk_set_root_frequencies; node v's row is P_v[c][x_father][.] as
+ *     stored on the device (plk_update_pmatrices or plk_set_pmatrix, per-branch models included).
+ * Two launches: the cumulative tables of the tree's branches, and one walk with a lane per site.
+ *
+ * Ops as for plk_pars_update: postorder, at most 3 sons per op (PLK_OP_ACCUMULATE ops append sons
+ * to their father: polytomies of any degree), every internal son formed by an earlier op of the
+ * same call; the last op's parent must equal `root` (PLK_ERR_ARG otherwise, and for a node of
+ * two fathers or outside [0, n_nodes)).  PLK_ERR_STATE when a branch of the tree has no P(t) or
+ * when the rates or the root frequencies are unset.
+ *
+ * flags = PLK_SIM_SET_TIPS: the state s of a tip is stored as the tip code state_code[s]
+ * (state_code == NULL: state s is code s), exactly as if plk_set_tip_codes had been called for
+ * every tip of the tree: every state_code[s] enters the compact numbering (in increasing code),
+ * every tip counts as set, and whatever new tip codes invalidate is invalidated.  Pattern weights
+ * are not touched.  PLK_ERR_STATE before plk_set_code_table, PLK_ERR_ARG for a state_code entry
+ * outside the code table.  Without the flag nothing of the handle but the simulation's own
+ * arrays changes.
+ *
+ * A multi-device handle fans the call out with each shard's site0 advanced by its first pattern,
+ * so states and codes are those of one device; one process per GPU passes its rank's first site
+ * as site0 and needs no communication.  Stream-ordered; synchronises before returning.  With
+ * plk_set_timing the table build is timed as PLK_TIME_TABLES and the walk as PLK_TIME_PARTIALS. */
+enum { PLK_SIM_SET_TIPS = 1u };
+int plk_simulate(plk_handle h, const plk_op* ops, int n_ops, int root, uint64_t seed, uint64_t replicate,
+                 int64_t site0, const uint8_t* state_code /* S, or NULL: state s is code s */, unsigned flags);
+/* The states (indices 0 .. S-1, not codes) of `node` and the rate classes of the last plk_simulate,
+ * one per pattern (a multi-device handle gathers the whole alignment).  PLK_ERR_STATE before any
+ * plk_simulate, PLK_ERR_ARG for a node outside the last simulated tree. */
+int plk_sim_get_states(plk_handle h, int node, uint8_t* states /* n_patterns, state indices */);
+int plk_sim_get_classes(plk_handle h, uint8_t* classes /* n_patterns */);
+/* Kernel launches (per shard) of the last plk_simulate on this handle. */
+int plk_sim_launches(plk_handle h, int64_t* launches);
 
 /* Instrumentation: HIP-event timing on the handle's stream of the kernels selected
  * by the mask given to plk_set_timing (0 = off).  Each timed launch adds an event
