@@ -20,6 +20,7 @@
 #include "plk_pair.hpp"
 #include "plk_pars.hpp"
 #include "plk_sim.hpp"
+#include "plk_smap.hpp"
 #include "plk_exchange.hpp"
 
 #include <hip/hip_runtime.h>
@@ -458,6 +459,29 @@ struct plk_handle_s {
   std::vector<int> sim_parent;          // father per node of that tree (-1: the root, or outside the tree)
   int sim_root = -1;                    // -1: no plk_simulate yet
   int64_t sim_launches = 0;             // kernel launches of the last plk_simulate
+  // stochastic mapping (plk_smap.hpp)
+  std::vector<std::vector<double> > smap_Q;  // per model: the generator (empty: none yet)
+  bool smap_tab_dirty = true;           // R and Rpow on the device predate a generator
+  bool smap_types_dirty = true;         // type_of on the device predates plk_smap_set_types
+  int smap_T = 0;                       // event types (0: plk_smap_set_types not called)
+  std::vector<uint8_t> smap_types;      // type_of [S][S]
+  char* d_smap_tab = nullptr;           // Q, R, RpowT of every model, type_of
+  double* d_smap_pois = nullptr;        // [node][C][N + 1]
+  char* d_smap_list = nullptr;          // a call's list
+  size_t d_smap_list_cap = 0;
+  char* d_smap_sums = nullptr;          // count and dwell sums, tallies, block totals, n_bad
+  size_t d_smap_sums_cap = 0;
+  char* d_smap_work = nullptr;          // one replicate's states and dwell row (calls without KEEP)
+  size_t d_smap_work_cap = 0;
+  char* d_smap_keep = nullptr;          // kept rows: states, n_jumps, counts, dwell
+  size_t d_smap_keep_cap = 0;
+  uint64_t smap_keep_r0 = 0;            // first kept replicate
+  int smap_keep_n = 0;                  // kept replicates (0: none)
+  int smap_keep_T = 0;                  // types of the kept rows
+  std::vector<int> smap_parent;         // father per node of the sampled tree (-1: the root, or outside it)
+  int smap_root = -1;                   // -1: no sums
+  int smap_sum_T = 0;                   // types of the sums
+  int64_t smap_launches = 0;            // kernel launches of the last plk_smap_sample
   // RELL resampling (plk_rell.hpp): site rows [rell_n_rows][n_pad] and replicate weights
   // [rell_R][n_pad], padding 0.0; a multi-device parent keeps the two counts only
   double* rell_rows = nullptr;
@@ -1272,7 +1296,8 @@ int plk_destroy(plk_handle h) {
                   h->d_cherry_rows, h->d_kidsl, h->d_cls, h->d_ucodes_dc, h->d_units_start, h->d_post, h->post_buf,
                   h->count_G, h->wmats, h->d_mapb, h->map_blk, h->d_mapreq, h->d_nni, h->nni_vit, h->d_pair,
                   h->rell_rows, h->rell_W, h->rell_stage, h->rell_bad, h->pars_sets, h->pars_scores, h->d_pars,
-                  h->d_pars_moves, h->sim_states, h->d_sim};
+                  h->d_pars_moves, h->sim_states, h->d_sim, h->d_smap_tab, h->d_smap_pois, h->d_smap_list,
+                  h->d_smap_sums, h->d_smap_work, h->d_smap_keep};
   for (void* p : bufs)
     if (p) hipFree(p);
   if (h->h_req) (void)hipHostFree(h->h_req);
@@ -6366,6 +6391,541 @@ int plk_sim_launches(plk_handle h, int64_t* launches) {
   if (!h || !launches) return fail(h, PLK_ERR_ARG, "null argument");
   if (!h->shards.empty()) return plk_sim_launches(h->shards[0], launches);
   *launches = h->sim_launches;
+  return PLK_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// Stochastic mapping (plk_smap.hpp): tables, one sampling launch over the call's replicates,
+// block totals.  Everything per pattern lives on the device as [row][k][n_pad] and is turned
+// into the caller's [row][pattern][k] by the getters.
+// ---------------------------------------------------------------------------
+namespace {
+
+struct SmapSums {  // offsets into d_smap_sums
+  size_t count, state, cls, dwell, blk, bad, end;
+  SmapSums(plk_handle h, int T) {
+    const size_t nn = (size_t)h->n_nodes, np = (size_t)h->n_pad;
+    count = 0;
+    state = count + nn * T * np * sizeof(uint32_t);
+    cls = state + nn * h->S * np * sizeof(uint32_t);
+    dwell = (cls + (size_t)h->C * np * sizeof(uint32_t) + 7) & ~(size_t)7;
+    blk = dwell + nn * h->S * np * sizeof(double);
+    bad = blk + nn * T * (size_t)h->n_blocks * sizeof(double);
+    end = bad + sizeof(unsigned long long);
+  }
+};
+
+struct SmapKeep {  // offsets into d_smap_keep for R replicates
+  size_t dwell, jumps, counts, states, end;
+  SmapKeep(plk_handle h, int T, size_t R) {
+    const size_t nn = (size_t)h->n_nodes, np = (size_t)h->n_pad;
+    dwell = 0;
+    jumps = dwell + R * nn * h->S * np * sizeof(double);
+    counts = jumps + R * nn * np * sizeof(uint16_t);
+    states = counts + R * nn * T * np * sizeof(uint16_t);
+    end = states + R * (nn + 1) * np;
+  }
+};
+
+size_t smap_tab_bytes(plk_handle h, size_t* off_r, size_t* off_t, size_t* off_type) {
+  const size_t SS = (size_t)h->S * h->S, M = (size_t)h->n_models;
+  *off_r = M * SS * sizeof(double);
+  *off_t = 2 * M * SS * sizeof(double);
+  *off_type = *off_t + M * kSmapN1 * SS * sizeof(double);
+  return *off_type + SS;
+}
+
+// device rows [K][n_pad] -> out [n_patterns][K]
+template <class V>
+int smap_rows_out(plk_handle h, const V* dev, int K, V* out) {
+  std::vector<V> buf((size_t)K * h->n_pad);
+  HIPCHK(h, hipMemcpy(buf.data(), dev, buf.size() * sizeof(V), hipMemcpyDeviceToHost));
+  for (int64_t p = 0; p < h->n_patterns; ++p)
+    for (int k = 0; k < K; ++k) out[p * K + k] = buf[(size_t)k * h->n_pad + p];
+  return PLK_OK;
+}
+
+int smap_have_sums(plk_handle h) {
+  if (h->smap_root < 0) return fail(h, PLK_ERR_STATE, "no plk_smap_sample yet");
+  hipSetDevice(h->device);
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return PLK_OK;
+}
+
+int smap_in_tree(plk_handle h, int node, bool branch) {
+  if (node < 0 || node >= h->n_nodes || (node == h->smap_root ? branch : h->smap_parent[(size_t)node] < 0))
+    return fail(h, PLK_ERR_ARG, "node %d is not %s the sampled tree", node, branch ? "a branch of" : "in");
+  return PLK_OK;
+}
+
+// total / p0: patterns per row of the caller's arrays and this handle's first pattern in them
+int smap_sums_local(plk_handle h, int n, const int32_t* nodes, bool branches, uint32_t* u32a, int Ka, size_t offa,
+                    double* f64b, uint32_t* u32b, int Kb, size_t offb, int64_t total, int64_t p0) {
+  int rc = smap_have_sums(h);
+  if (rc) return rc;
+  for (int i = 0; i < n; ++i)
+    if ((rc = smap_in_tree(h, nodes[i], branches))) return rc;
+  const size_t np = (size_t)h->n_pad;
+  for (int i = 0; i < n; ++i) {
+    const size_t v = (size_t)nodes[i];
+    if (u32a && (rc = smap_rows_out(h, (const uint32_t*)(h->d_smap_sums + offa) + v * Ka * np, Ka,
+                                    u32a + ((size_t)i * total + p0) * Ka)))
+      return rc;
+    if (f64b && (rc = smap_rows_out(h, (const double*)(h->d_smap_sums + offb) + v * Kb * np, Kb,
+                                    f64b + ((size_t)i * total + p0) * Kb)))
+      return rc;
+  }
+  if (u32b) return smap_rows_out(h, (const uint32_t*)(h->d_smap_sums + offb), Kb, u32b + (size_t)p0 * Kb);
+  return PLK_OK;
+}
+
+// blocks: [branch][T][nB_total], this handle's blocks from B0
+int smap_totals_local(plk_handle h, int n, const int32_t* branches, double* blocks, int64_t nB_total, int64_t B0) {
+  int rc = smap_have_sums(h);
+  if (rc) return rc;
+  for (int i = 0; i < n; ++i)
+    if ((rc = smap_in_tree(h, branches[i], true))) return rc;
+  const int T = h->smap_sum_T, nB = h->n_blocks;
+  const SmapSums o(h, T);
+  std::vector<double> buf((size_t)h->n_nodes * T * nB);
+  HIPCHK(h, hipMemcpy(buf.data(), h->d_smap_sums + o.blk, buf.size() * sizeof(double), hipMemcpyDeviceToHost));
+  for (int i = 0; i < n; ++i)
+    for (int k = 0; k < T; ++k)
+      std::copy(buf.begin() + ((size_t)branches[i] * T + k) * nB, buf.begin() + ((size_t)branches[i] * T + k + 1) * nB,
+                blocks + ((size_t)i * T + k) * nB_total + B0);
+  return PLK_OK;
+}
+
+// the kept rows of `replicate`: its index among them
+int smap_kept(plk_handle h, uint64_t replicate, size_t* r) {
+  int rc = smap_have_sums(h);
+  if (rc) return rc;
+  if (!h->smap_keep_n || replicate < h->smap_keep_r0 || replicate - h->smap_keep_r0 >= (uint64_t)h->smap_keep_n)
+    return fail(h, PLK_ERR_ARG, "replicate %llu is not kept (PLK_SMAP_KEEP)", (unsigned long long)replicate);
+  *r = (size_t)(replicate - h->smap_keep_r0);
+  return PLK_OK;
+}
+
+int smap_sample_local(plk_handle h, int root, int n, const int32_t* branch, const int32_t* model, const double* t,
+                      uint64_t seed, uint64_t replicate0, int n_rep, int64_t site0, unsigned flags) {
+  if (flags & ~(unsigned)(PLK_SMAP_ACCUMULATE | PLK_SMAP_KEEP)) return fail(h, PLK_ERR_ARG, "unknown flags 0x%x", flags);
+  if (n_rep <= 0) return fail(h, PLK_ERR_ARG, "n_replicates %d not > 0", n_rep);
+  if (site0 < 0) return fail(h, PLK_ERR_ARG, "negative site0");
+  if (n <= 0 || !branch || !t) return fail(h, PLK_ERR_ARG, "bad branch list (%d branches)", n);
+  if (h->flags & (PLK_FLAG_LNL_ONLY | PLK_FLAG_SUBTREE_PATTERNS))
+    return fail(h, PLK_ERR_UNSUPPORTED, "stochastic mapping reads every lower partial at full length "
+                "(no PLK_FLAG_LNL_ONLY, no PLK_FLAG_SUBTREE_PATTERNS)");
+  const int S = h->S, C = h->C, nt = h->n_tips, nn = h->n_nodes, SS = S * S;
+  if (h->trav_ops.empty()) return fail(h, PLK_ERR_STATE, "no traversal yet (plk_update_partials)");
+  const TopoView tv(h->topo_kids, h->trav_ops.back().parent);
+  if (root != tv.root) return fail(h, PLK_ERR_ARG, "node %d is not the root %d of the last traversal", root, tv.root);
+  const std::vector<char> in_tree = tv.in_tree();
+  std::vector<int> at((size_t)nn, -1);  // node -> its entry of the caller's list
+  for (int i = 0; i < n; ++i) {
+    const int v = branch[i];
+    if (v < 0 || v >= nn || v == root || !in_tree[v]) return fail(h, PLK_ERR_ARG, "node %d is not a branch of the current tree", v);
+    if (at[v] >= 0) return fail(h, PLK_ERR_ARG, "branch %d is listed twice", v);
+    const int m = model ? model[i] : 0;
+    if (m < 0 || m >= h->n_models) return fail(h, PLK_ERR_ARG, "model %d out of range", m);
+    if (!(t[i] >= 0.0) || !(t[i] < HUGE_VAL)) return fail(h, PLK_ERR_ARG, "branch length %g not in [0, inf)", t[i]);
+    at[v] = i;
+  }
+  for (int v = 0; v < nn; ++v)
+    if (in_tree[v] && v != root && at[v] < 0) return fail(h, PLK_ERR_ARG, "branch %d of the tree is not listed", v);
+  if (!h->rates_set) return fail(h, PLK_ERR_STATE, "category rates not set");
+  if (!h->pi_set) return fail(h, PLK_ERR_STATE, "root frequencies not set");
+  if (!h->smap_T) return fail(h, PLK_ERR_STATE, "no event types (plk_smap_set_types)");
+  for (int i = 0; i < n; ++i) {
+    if (!h->pmat_valid[branch[i]]) return fail(h, PLK_ERR_STATE, "branch %d has no transition matrix", branch[i]);
+    const int m = model ? model[i] : 0;
+    if (h->smap_Q.empty() || h->smap_Q[(size_t)m].empty())
+      return fail(h, PLK_ERR_STATE, "model %d has no generator (plk_smap_set_generator)", m);
+  }
+  hipSetDevice(h->device);
+  int rc;
+  {
+    std::vector<double> rates((size_t)C);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(rates.data(), h->rates, (size_t)C * sizeof(double), hipMemcpyDeviceToHost));
+    const double rmax = *std::max_element(rates.begin(), rates.end());
+    for (int i = 0; i < n; ++i) {
+      const std::vector<double>& Q = h->smap_Q[(size_t)(model ? model[i] : 0)];
+      double mu = 0.0;
+      for (int x = 0; x < S; ++x) mu = std::max(mu, -Q[(size_t)x * S + x]);
+      if (!(mu * rmax * t[i] <= kSmapMaxLambda))
+        return fail(h, PLK_ERR_UNSUPPORTED, "branch %d: mu r t = %g exceeds %g (uniformisation is cut at %d jumps)", branch[i],
+                    mu * rmax * t[i], kSmapMaxLambda, kSmapMaxJumps);
+    }
+  }
+  // the list, fathers first
+  std::vector<SmapEntry> list;
+  std::vector<int> internal, st(1, root);
+  while (!st.empty()) {
+    const int f = st.back();
+    st.pop_back();
+    if (f >= nt) internal.push_back(f);
+    for (int v : tv.kids[f]) {
+      SmapEntry e;
+      std::memset(&e, 0, sizeof(e));
+      e.node = v;
+      e.father = f;
+      e.model = model ? model[at[v]] : 0;
+      e.is_tip = v < nt;
+      e.child = v < nt ? v : v - nt;
+      e.t = t[at[v]];
+      list.push_back(e);
+      st.push_back(v);
+    }
+  }
+  if ((rc = ensure_partials(h, internal))) return rc;
+  for (int v : internal)
+    if (!h->materialized[v - nt]) return fail(h, PLK_ERR_STATE, "node %d has no partial", v);
+  const int T = h->smap_T;
+  const int64_t totals_wgs = (int64_t)list.size() * T * h->n_blocks;
+  if (totals_wgs > 0x7fffffff)
+    return fail(h, PLK_ERR_UNSUPPORTED, "%zu branches x %d types x %d blocks exceed one launch's workgroups", list.size(), T,
+                h->n_blocks);
+  const bool keep = (flags & PLK_SMAP_KEEP) != 0;
+  const bool fresh = !(flags & PLK_SMAP_ACCUMULATE) || h->smap_root != root || h->smap_sum_T != T;
+  h->smap_root = -1;
+  h->smap_keep_n = 0;
+  // buffers
+  size_t off_r, off_t, off_type;
+  const size_t tab_bytes = smap_tab_bytes(h, &off_r, &off_t, &off_type);
+  if (!h->d_smap_tab) {
+    if ((rc = dalloc(h, (void**)&h->d_smap_tab, tab_bytes))) return rc;
+    h->smap_tab_dirty = h->smap_types_dirty = true;
+  }
+  if (!h->d_smap_pois && (rc = dalloc(h, (void**)&h->d_smap_pois, (size_t)nn * C * kSmapN1 * sizeof(double)))) return rc;
+  const SmapSums so(h, T);
+  const size_t sums_before = h->d_smap_sums_cap;
+  if ((rc = ensure_cap(h, (void**)&h->d_smap_sums, &h->d_smap_sums_cap, so.end))) return rc;
+  const bool zero = fresh || h->d_smap_sums_cap != sums_before;
+  if ((rc = ensure_cap(h, (void**)&h->d_smap_list, &h->d_smap_list_cap, list.size() * sizeof(SmapEntry)))) return rc;
+  const size_t np = (size_t)h->n_pad;
+  const SmapKeep ko(h, T, (size_t)n_rep);
+  const size_t work_dwell = (size_t)S * np * sizeof(double);
+  if (keep) {
+    if ((rc = ensure_cap(h, (void**)&h->d_smap_keep, &h->d_smap_keep_cap, ko.end))) return rc;
+  } else if ((rc = ensure_cap(h, (void**)&h->d_smap_work, &h->d_smap_work_cap, work_dwell + (size_t)(nn + 1) * np))) {
+    return rc;
+  }
+  if (h->smap_tab_dirty) {
+    std::vector<double> Q((size_t)h->n_models * SS, 0.0);
+    for (int m = 0; m < h->n_models; ++m)
+      if (!h->smap_Q[(size_t)m].empty()) std::copy(h->smap_Q[(size_t)m].begin(), h->smap_Q[(size_t)m].end(), Q.begin() + (size_t)m * SS);
+    HIPCHK(h, hipMemcpy(h->d_smap_tab, Q.data(), Q.size() * sizeof(double), hipMemcpyHostToDevice));
+  }
+  if (h->smap_types_dirty)
+    HIPCHK(h, hipMemcpy(h->d_smap_tab + off_type, h->smap_types.data(), (size_t)SS, hipMemcpyHostToDevice));
+  HIPCHK(h, hipMemcpyAsync(h->d_smap_list, list.data(), list.size() * sizeof(SmapEntry), hipMemcpyHostToDevice, h->stream));
+  if (zero) HIPCHK(h, hipMemsetAsync(h->d_smap_sums, 0, so.end, h->stream));
+  SmapArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.Q = reinterpret_cast<const double*>(h->d_smap_tab);
+  a.R = reinterpret_cast<double*>(h->d_smap_tab + off_r);
+  a.RpowT = reinterpret_cast<double*>(h->d_smap_tab + off_t);
+  a.type_of = reinterpret_cast<const uint8_t*>(h->d_smap_tab + off_type);
+  a.pois = h->d_smap_pois;
+  a.rates = h->rates;
+  a.list = reinterpret_cast<const SmapEntry*>(h->d_smap_list);
+  a.n_list = (int32_t)list.size();
+  a.S = S;
+  a.C = C;
+  a.T = T;
+  a.n_models = h->n_models;
+  // (the rows of a model without a generator are read by no listed branch)
+  a.rpow_blocks = h->smap_tab_dirty ? h->n_models * S : 0;
+  a.partials = h->partials;
+  a.codes = h->codes;
+  a.code_table = h->code_table;
+  a.pmats = h->pmats;
+  a.pi = h->pi;
+  a.probs = h->probs;
+  a.slot_stride = h->slot_stride;
+  a.n_pad = h->n_pad;
+  a.n_patterns = h->n_patterns;
+  a.root = root;
+  a.root_slot = root - nt;
+  a.n_nodes = nn;
+  a.n_rep = n_rep;
+  a.keep = keep;
+  a.seed = seed;
+  a.replicate0 = replicate0;
+  a.site0 = (uint64_t)site0;
+  if (keep) {
+    a.dwell = reinterpret_cast<double*>(h->d_smap_keep + ko.dwell);
+    a.jumps = reinterpret_cast<uint16_t*>(h->d_smap_keep + ko.jumps);
+    a.counts = reinterpret_cast<uint16_t*>(h->d_smap_keep + ko.counts);
+    a.states = reinterpret_cast<uint8_t*>(h->d_smap_keep + ko.states);
+  } else {
+    a.dwell = reinterpret_cast<double*>(h->d_smap_work);
+    a.states = reinterpret_cast<uint8_t*>(h->d_smap_work + work_dwell);
+  }
+  a.count_sum = reinterpret_cast<uint32_t*>(h->d_smap_sums + so.count);
+  a.state_tally = reinterpret_cast<uint32_t*>(h->d_smap_sums + so.state);
+  a.class_tally = reinterpret_cast<uint32_t*>(h->d_smap_sums + so.cls);
+  a.dwell_sum = reinterpret_cast<double*>(h->d_smap_sums + so.dwell);
+  a.n_bad = reinterpret_cast<unsigned long long*>(h->d_smap_sums + so.bad);
+  {
+    TimedSpan span(h, PLK_TIME_TABLES, 3);
+    const unsigned blocks = (unsigned)(a.rpow_blocks + (list.size() * C + 63) / 64);
+    smap_table_kernel<<<blocks, 64, 0, h->stream>>>(a);
+    HIPCHK(h, hipGetLastError());
+    if (span.stop()) h->n_table_launches++;
+  }
+  {
+    TimedSpan span(h, PLK_TIME_PARTIALS, 0);
+    const unsigned blocks = (unsigned)((h->n_patterns + kSmapThreads - 1) / kSmapThreads);
+    const size_t lds = ((size_t)h->n_models * (kSmapN1 + 1) * SS) * sizeof(double);
+    if (S == 4 && lds <= kSmapLdsMax && !tune_is("SMAP_LDS", '0'))
+      smap_sample_kernel<4, true><<<blocks, kSmapThreads, lds, h->stream>>>(a);
+    else if (S == 4)
+      smap_sample_kernel<4, false><<<blocks, kSmapThreads, 0, h->stream>>>(a);
+    else if (S == 20)
+      smap_sample_kernel<20, false><<<blocks, kSmapThreads, 0, h->stream>>>(a);
+    else if (S == 64)
+      smap_sample_kernel<64, false><<<blocks, kSmapThreads, 0, h->stream>>>(a);
+    else
+      smap_sample_kernel<0, false><<<blocks, kSmapThreads, 0, h->stream>>>(a);
+    HIPCHK(h, hipGetLastError());
+    if (span.stop()) h->n_launches++;
+  }
+  {
+    TimedSpan span(h, PLK_TIME_ROOT, 2);
+    // one workgroup per (listed branch, type, root block), all on grid.x; the rows of the root and of
+    // nodes outside the tree stay 0
+    smap_totals_kernel<<<(unsigned)totals_wgs, 256, 0, h->stream>>>(a.count_sum, h->weights,
+                                                                     reinterpret_cast<double*>(h->d_smap_sums + so.blk), a.list,
+                                                                     T, h->n_pad, h->n_patterns, h->n_blocks);
+    HIPCHK(h, hipGetLastError());
+    span.stop();
+  }
+  h->smap_launches = 3;
+  HIPCHK(h, hipStreamSynchronize(h->stream));  // the list is a local
+  h->smap_tab_dirty = h->smap_types_dirty = false;
+  h->smap_parent = tv.parent;
+  for (int v = 0; v < nn; ++v)
+    if (!in_tree[v]) h->smap_parent[(size_t)v] = -1;
+  h->smap_root = root;
+  h->smap_sum_T = T;
+  if (keep) {
+    h->smap_keep_r0 = replicate0;
+    h->smap_keep_n = n_rep;
+    h->smap_keep_T = T;
+  }
+  return PLK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int plk_smap_set_generator(plk_handle h, int model, const double* Q) {
+  env_refresh();
+  if (h && !h->shards.empty()) return multi_each(h, [&](plk_handle x) { return plk_smap_set_generator(x, model, Q); });
+  if (!h || !Q || model < 0 || model >= h->n_models) return fail(h, PLK_ERR_ARG, "bad generator (model %d)", model);
+  const int S = h->S;
+  double mu = 0.0;
+  for (int x = 0; x < S; ++x) {
+    for (int y = 0; y < S; ++y) {
+      const double q = Q[(size_t)x * S + y];
+      if (!(q > -HUGE_VAL && q < HUGE_VAL)) return fail(h, PLK_ERR_ARG, "generator entry [%d][%d] is not finite", x, y);
+      if (x != y && q < 0.0) return fail(h, PLK_ERR_ARG, "generator entry [%d][%d] = %g is below 0", x, y, q);
+    }
+    mu = std::max(mu, -Q[(size_t)x * S + x]);
+  }
+  if (!(mu > 0.0)) return fail(h, PLK_ERR_ARG, "the generator has no positive rate");
+  if (h->smap_Q.empty()) h->smap_Q.assign((size_t)h->n_models, std::vector<double>());
+  h->smap_Q[(size_t)model].assign(Q, Q + (size_t)S * S);
+  h->smap_tab_dirty = true;
+  return PLK_OK;
+}
+
+int plk_smap_set_types(plk_handle h, int n_types, const uint8_t* type_of) {
+  env_refresh();
+  if (h && !h->shards.empty()) return multi_each(h, [&](plk_handle x) { return plk_smap_set_types(x, n_types, type_of); });
+  if (!h || !type_of) return fail(h, PLK_ERR_ARG, "null argument");
+  if (n_types < 1 || n_types > kMapMaxTypes) return fail(h, PLK_ERR_ARG, "n_types %d not in [1, %d]", n_types, kMapMaxTypes);
+  const size_t SS = (size_t)h->S * h->S;
+  for (size_t e = 0; e < SS; ++e)
+    if (type_of[e] > n_types) return fail(h, PLK_ERR_ARG, "type_of[%zu][%zu] = %d exceeds %d types", e / h->S, e % h->S, type_of[e], n_types);
+  h->smap_types.assign(type_of, type_of + SS);
+  h->smap_T = n_types;
+  h->smap_types_dirty = true;
+  return PLK_OK;
+}
+
+int plk_smap_sample(plk_handle h, int root, int n, const int32_t* branch, const int32_t* model, const double* t,
+                    uint64_t seed, uint64_t replicate0, int n_replicates, int64_t site0, unsigned flags) {
+  env_refresh();
+  if (!h) return fail(nullptr, PLK_ERR_ARG, "null handle");
+  if (!h->shards.empty())
+    return multi_slices(h, [&](plk_handle x, int64_t a) {
+      return smap_sample_local(x, root, n, branch, model, t, seed, replicate0, n_replicates, site0 + a, flags);
+    });
+  // (under a communicator: the rank's own patterns from its first site, no collective call)
+  return smap_sample_local(h, root, n, branch, model, t, seed, replicate0, n_replicates, site0, flags);
+}
+
+int plk_smap_get_sums(plk_handle h, int n_branches, const int32_t* branches, uint32_t* count_sum, double* dwell_sum) {
+  env_refresh();
+  if (!h || n_branches <= 0 || !branches || (!count_sum && !dwell_sum)) return fail(h, PLK_ERR_ARG, "bad request");
+  auto local = [&](plk_handle x, int64_t p0) {
+    const SmapSums o(x, x->smap_sum_T);
+    return smap_sums_local(x, n_branches, branches, true, count_sum, x->smap_sum_T, o.count, dwell_sum, nullptr, x->S, o.dwell,
+                           h->n_patterns, p0);
+  };
+  return h->shards.empty() ? local(h, 0) : multi_slices(h, local);
+}
+
+int plk_smap_get_tallies(plk_handle h, int n_nodes, const int32_t* nodes, uint32_t* state_tally, uint32_t* class_tally) {
+  env_refresh();
+  if (!h || n_nodes < 0 || (n_nodes > 0 && !nodes) || (!state_tally && !class_tally) || (state_tally && n_nodes == 0))
+    return fail(h, PLK_ERR_ARG, "bad request");
+  auto local = [&](plk_handle x, int64_t p0) {
+    const SmapSums o(x, x->smap_sum_T);
+    return smap_sums_local(x, state_tally ? n_nodes : 0, nodes, false, state_tally, x->S, o.state, nullptr, class_tally, x->C,
+                           o.cls, h->n_patterns, p0);
+  };
+  return h->shards.empty() ? local(h, 0) : multi_slices(h, local);
+}
+
+int plk_smap_get_totals(plk_handle h, int n_branches, const int32_t* branches, double* totals) {
+  env_refresh();
+  if (!h || n_branches <= 0 || !branches || !totals) return fail(h, PLK_ERR_ARG, "bad request");
+  const bool multi = !h->shards.empty();
+  const int T = multi ? h->shards[0]->smap_sum_T : h->smap_sum_T;
+  // block sums of every shard at their global block index, added in that order
+  const int64_t nB = (h->n_patterns + kRootBlock - 1) / kRootBlock;
+  std::vector<double> blocks((size_t)n_branches * std::max(T, 1) * nB, 0.0);
+  const int rc = multi ? multi_slices(h, [&](plk_handle x, int64_t a) {
+    return smap_totals_local(x, n_branches, branches, blocks.data(), nB, a / kRootBlock);
+  }) : smap_totals_local(h, n_branches, branches, blocks.data(), nB, 0);
+  if (rc) return rc;
+  for (size_t r = 0; r < (size_t)n_branches * T; ++r) {
+    double s = 0.0;
+    for (int64_t B = 0; B < nB; ++B) s += blocks[r * nB + B];
+    totals[r] = s;
+  }
+  return PLK_OK;
+}
+
+int plk_smap_get_states(plk_handle h, uint64_t replicate, int node, uint8_t* states) {
+  env_refresh();
+  if (!h || !states) return fail(h, PLK_ERR_ARG, "null argument");
+  if (!h->shards.empty()) return multi_slices(h, [&](plk_handle x, int64_t a) { return plk_smap_get_states(x, replicate, node, states + a); });
+  size_t r;
+  int rc = smap_kept(h, replicate, &r);
+  if (rc || (rc = smap_in_tree(h, node, false))) return rc;
+  const SmapKeep o(h, h->smap_keep_T, (size_t)h->smap_keep_n);
+  return smap_rows_out(h, (const uint8_t*)(h->d_smap_keep + o.states) + (r * (h->n_nodes + 1) + node) * (size_t)h->n_pad, 1, states);
+}
+
+int plk_smap_get_classes(plk_handle h, uint64_t replicate, uint8_t* classes) {
+  env_refresh();
+  if (!h || !classes) return fail(h, PLK_ERR_ARG, "null argument");
+  if (!h->shards.empty()) return multi_slices(h, [&](plk_handle x, int64_t a) { return plk_smap_get_classes(x, replicate, classes + a); });
+  size_t r;
+  const int rc = smap_kept(h, replicate, &r);
+  if (rc) return rc;
+  const SmapKeep o(h, h->smap_keep_T, (size_t)h->smap_keep_n);
+  return smap_rows_out(h, (const uint8_t*)(h->d_smap_keep + o.states) + (r * (h->n_nodes + 1) + h->n_nodes) * (size_t)h->n_pad, 1, classes);
+}
+
+int plk_smap_get_jumps(plk_handle h, uint64_t replicate, int branch, uint16_t* n_jumps) {
+  env_refresh();
+  if (!h || !n_jumps) return fail(h, PLK_ERR_ARG, "null argument");
+  if (!h->shards.empty()) return multi_slices(h, [&](plk_handle x, int64_t a) { return plk_smap_get_jumps(x, replicate, branch, n_jumps + a); });
+  size_t r;
+  int rc = smap_kept(h, replicate, &r);
+  if (rc || (rc = smap_in_tree(h, branch, true))) return rc;
+  const SmapKeep o(h, h->smap_keep_T, (size_t)h->smap_keep_n);
+  return smap_rows_out(h, (const uint16_t*)(h->d_smap_keep + o.jumps) + (r * h->n_nodes + branch) * (size_t)h->n_pad, 1, n_jumps);
+}
+
+int plk_smap_get_counts(plk_handle h, uint64_t replicate, int branch, uint16_t* counts) {
+  env_refresh();
+  if (!h || !counts) return fail(h, PLK_ERR_ARG, "null argument");
+  if (!h->shards.empty())
+    return multi_slices(h, [&](plk_handle x, int64_t a) { return plk_smap_get_counts(x, replicate, branch, counts + a * x->smap_keep_T); });
+  size_t r;
+  int rc = smap_kept(h, replicate, &r);
+  if (rc || (rc = smap_in_tree(h, branch, true))) return rc;
+  const int T = h->smap_keep_T;
+  const SmapKeep o(h, T, (size_t)h->smap_keep_n);
+  return smap_rows_out(h, (const uint16_t*)(h->d_smap_keep + o.counts) + (r * h->n_nodes + branch) * (size_t)T * h->n_pad, T, counts);
+}
+
+int plk_smap_get_dwell(plk_handle h, uint64_t replicate, int branch, double* dwell) {
+  env_refresh();
+  if (!h || !dwell) return fail(h, PLK_ERR_ARG, "null argument");
+  if (!h->shards.empty())
+    return multi_slices(h, [&](plk_handle x, int64_t a) { return plk_smap_get_dwell(x, replicate, branch, dwell + a * x->S); });
+  size_t r;
+  int rc = smap_kept(h, replicate, &r);
+  if (rc || (rc = smap_in_tree(h, branch, true))) return rc;
+  const SmapKeep o(h, h->smap_keep_T, (size_t)h->smap_keep_n);
+  return smap_rows_out(h, (const double*)(h->d_smap_keep + o.dwell) + (r * h->n_nodes + branch) * (size_t)h->S * h->n_pad, h->S, dwell);
+}
+
+int plk_smap_get_tables(plk_handle h, int model, double* R, double* Rpow, int branch, double* pois) {
+  env_refresh();
+  if (h && !h->shards.empty()) return multi_forward(h, plk_smap_get_tables(h->shards[0], model, R, Rpow, branch, pois));
+  if (!h) return fail(h, PLK_ERR_ARG, "null handle");
+  int rc = smap_have_sums(h);
+  if (rc) return rc;
+  const int S = h->S, SS = S * S;
+  size_t off_r, off_t, off_type;
+  smap_tab_bytes(h, &off_r, &off_t, &off_type);
+  if (R || Rpow) {
+    if (model < 0 || model >= h->n_models || h->smap_Q[(size_t)model].empty())
+      return fail(h, PLK_ERR_ARG, "model %d has no generator", model);
+    if (R) HIPCHK(h, hipMemcpy(R, h->d_smap_tab + off_r + (size_t)model * SS * sizeof(double), SS * sizeof(double), hipMemcpyDeviceToHost));
+    if (Rpow) {
+      std::vector<double> T((size_t)kSmapN1 * SS);
+      HIPCHK(h, hipMemcpy(T.data(), h->d_smap_tab + off_t + (size_t)model * kSmapN1 * SS * sizeof(double), T.size() * sizeof(double),
+                          hipMemcpyDeviceToHost));
+      for (int n = 0; n < kSmapN1; ++n)
+        for (int b = 0; b < S; ++b)
+          for (int y = 0; y < S; ++y) Rpow[(size_t)n * SS + y * S + b] = T[(size_t)n * SS + b * S + y];
+    }
+  }
+  if (pois) {
+    if ((rc = smap_in_tree(h, branch, true))) return rc;
+    HIPCHK(h, hipMemcpy(pois, h->d_smap_pois + (size_t)branch * h->C * kSmapN1, (size_t)h->C * kSmapN1 * sizeof(double),
+                        hipMemcpyDeviceToHost));
+  }
+  return PLK_OK;
+}
+
+int plk_smap_bad(plk_handle h, int64_t* n_bad) {
+  env_refresh();
+  if (!h || !n_bad) return fail(h, PLK_ERR_ARG, "null argument");
+  if (!h->shards.empty()) {
+    int64_t s = 0;
+    for (plk_handle x : h->shards) {
+      int64_t v = 0;
+      if (const int rc = plk_smap_bad(x, &v)) return multi_forward(h, rc);
+      s += v;
+    }
+    *n_bad = s;
+    return PLK_OK;
+  }
+  const int rc = smap_have_sums(h);
+  if (rc) return rc;
+  unsigned long long v = 0;
+  HIPCHK(h, hipMemcpy(&v, h->d_smap_sums + SmapSums(h, h->smap_sum_T).bad, sizeof(v), hipMemcpyDeviceToHost));
+  *n_bad = (int64_t)v;
+  return PLK_OK;
+}
+
+int plk_smap_launches(plk_handle h, int64_t* launches) {
+  if (!h || !launches) return fail(h, PLK_ERR_ARG, "null argument");
+  if (!h->shards.empty()) return plk_smap_launches(h->shards[0], launches);
+  *launches = h->smap_launches;
   return PLK_OK;
 }
 

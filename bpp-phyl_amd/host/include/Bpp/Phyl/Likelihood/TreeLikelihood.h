@@ -268,6 +268,21 @@ class AbstractPlkTreeLikelihood : public virtual TreeLikelihood {
   // register with fewer types than an earlier one is padded with empty types, one with more
   // needs another likelihood object.
   std::vector<double> computeBranchCounts(const std::vector<int>& nodeIds, SubstitutionCount& count) const;
+  // Stochastic mapping (Mapping/DeviceStochasticMapping.h) reads every lower partial at full
+  // length, which this likelihood's own engine does not keep for the shapes the fused kernels serve
+  // (PLK_FLAG_LNL_ONLY).  A second handle with this likelihood's data, models, rates, root
+  // frequencies and P(t) of the current parameters, created with PLK_FLAG_SCALING and after one
+  // traversal: the caller owns it (plk_destroy).  branch / model / length list every non-root node
+  // as plk_smap_sample takes them; engineOfId maps node ids to engine indices.
+  struct MappingEngine {
+    plk_handle_s* handle = nullptr;
+    int root = -1;
+    std::vector<int> branchIds;
+    std::vector<int32_t> branch, model;
+    std::vector<double> length;
+    std::map<int, int> engineOfId;
+  };
+  MappingEngine createMappingEngine() const;
   bool isLeafNode(int nodeId) const { return tree_->getNode(nodeId)->isLeaf(); }
   std::vector<int> getInnerNodesId() const;
   // a leaf's init values per distinct pattern, [pattern][state]

@@ -28,6 +28,8 @@ PLK_DERIV_P, PLK_DERIV_DP, PLK_DERIV_D2P = 1, 2, 4
 PLK_OP_ACCUMULATE = 1
 PLK_TIME_PARTIALS, PLK_TIME_PMAT, PLK_TIME_ROOT, PLK_TIME_TABLES = 1, 2, 4, 8
 PLK_SIM_SET_TIPS = 1
+PLK_SMAP_ACCUMULATE, PLK_SMAP_KEEP = 1, 2
+PLK_SMAP_MAX_JUMPS = 128
 
 # every symbol include/plk.h declares
 EXPORTS = [
@@ -47,7 +49,9 @@ EXPORTS = [
     "plk_site_row_from_root", "plk_nni_site_rows", "plk_set_replicate_weights", "plk_replicate_sums",
     "plk_replicate_passes", "plk_pars_set_code_masks", "plk_pars_update", "plk_pars_score", "plk_pars_get_edge",
     "plk_pars_nni_scores", "plk_pars_launches", "plk_simulate", "plk_sim_get_states", "plk_sim_get_classes",
-    "plk_sim_launches",
+    "plk_sim_launches", "plk_smap_set_generator", "plk_smap_set_types", "plk_smap_sample", "plk_smap_get_sums",
+    "plk_smap_get_tallies", "plk_smap_get_totals", "plk_smap_get_states", "plk_smap_get_classes", "plk_smap_get_jumps",
+    "plk_smap_get_counts", "plk_smap_get_dwell", "plk_smap_get_tables", "plk_smap_bad", "plk_smap_launches",
 ]
 
 
@@ -168,6 +172,21 @@ def load(path: str = LIB_PATH) -> ct.CDLL:
         "plk_sim_get_states": ([ct.c_void_p, ct.c_int, P(ct.c_uint8)], ct.c_int),
         "plk_sim_get_classes": ([ct.c_void_p, P(ct.c_uint8)], ct.c_int),
         "plk_sim_launches": ([ct.c_void_p, P(ct.c_int64)], ct.c_int),
+        "plk_smap_set_generator": ([ct.c_void_p, ct.c_int, dp], ct.c_int),
+        "plk_smap_set_types": ([ct.c_void_p, ct.c_int, P(ct.c_uint8)], ct.c_int),
+        "plk_smap_sample": ([ct.c_void_p, ct.c_int, ct.c_int, ip, ip, dp, ct.c_uint64, ct.c_uint64, ct.c_int, ct.c_int64,
+                             ct.c_uint], ct.c_int),
+        "plk_smap_get_sums": ([ct.c_void_p, ct.c_int, ip, P(ct.c_uint32), dp], ct.c_int),
+        "plk_smap_get_tallies": ([ct.c_void_p, ct.c_int, ip, P(ct.c_uint32), P(ct.c_uint32)], ct.c_int),
+        "plk_smap_get_totals": ([ct.c_void_p, ct.c_int, ip, dp], ct.c_int),
+        "plk_smap_get_states": ([ct.c_void_p, ct.c_uint64, ct.c_int, P(ct.c_uint8)], ct.c_int),
+        "plk_smap_get_classes": ([ct.c_void_p, ct.c_uint64, P(ct.c_uint8)], ct.c_int),
+        "plk_smap_get_jumps": ([ct.c_void_p, ct.c_uint64, ct.c_int, P(ct.c_uint16)], ct.c_int),
+        "plk_smap_get_counts": ([ct.c_void_p, ct.c_uint64, ct.c_int, P(ct.c_uint16)], ct.c_int),
+        "plk_smap_get_dwell": ([ct.c_void_p, ct.c_uint64, ct.c_int, dp], ct.c_int),
+        "plk_smap_get_tables": ([ct.c_void_p, ct.c_int, dp, dp, ct.c_int, dp], ct.c_int),
+        "plk_smap_bad": ([ct.c_void_p, P(ct.c_int64)], ct.c_int),
+        "plk_smap_launches": ([ct.c_void_p, P(ct.c_int64)], ct.c_int),
         "plk_kernel_path": ([ct.c_void_p], ct.c_char_p),
         "plk_compressed_work": ([ct.c_void_p, P(ct.c_int64)], ct.c_int),
         "plk_evaluate": ([ct.c_void_p, ct.c_int, ip, ip, dp, P(plk_op), ct.c_int, ct.c_int, dp, dp], ct.c_int),
@@ -792,6 +811,110 @@ class Engine:
     def sim_launches(self) -> int:
         n = ct.c_int64(0)
         self._chk(self.lib.plk_sim_launches(self.h, ct.byref(n)))
+        return n.value
+
+    # Stochastic mapping: sampled histories on every branch, sums over replicates on the device
+
+    def smap_set_generator(self, model: int, Q: np.ndarray):
+        """plk_smap_set_generator: the generator Q [S, S] of `model` (rows summing to 0)."""
+        q = np.ascontiguousarray(Q, dtype=np.float64)
+        assert q.shape == (self.S, self.S)
+        self._chk(self.lib.plk_smap_set_generator(self.h, int(model), _d(q)))
+
+    def smap_set_types(self, n_types: int, type_of: np.ndarray):
+        """plk_smap_set_types: type_of [S, S] in 0..n_types (0: the change x -> y is not counted)."""
+        ty = np.ascontiguousarray(type_of, dtype=np.uint8)
+        assert ty.shape == (self.S, self.S)
+        self._chk(self.lib.plk_smap_set_types(self.h, int(n_types), ty.ctypes.data_as(ct.POINTER(ct.c_uint8))))
+        self.smap_T = int(n_types)
+
+    def smap_sample(self, root: int, branches, t, seed: int, replicate0: int = 0, n_replicates: int = 1, site0: int = 0,
+                    models=None, accumulate: bool = False, keep: bool = False):
+        """plk_smap_sample: replicates replicate0 .. replicate0 + n_replicates - 1 of the histories on
+        the tree of the last update_partials; branches / t / models list every non-root node."""
+        b = np.ascontiguousarray(branches, dtype=np.int32).ravel()
+        tt = np.ascontiguousarray(t, dtype=np.float64).ravel()
+        if len(tt) != len(b):
+            raise ValueError("t has one entry per branch")
+        ip = ct.POINTER(ct.c_int32)
+        mp = None
+        if models is not None:
+            m = np.ascontiguousarray(models, dtype=np.int32).ravel()
+            if len(m) != len(b):
+                raise ValueError("models has one entry per branch")
+            mp = m.ctypes.data_as(ip)
+        flags = (PLK_SMAP_ACCUMULATE if accumulate else 0) | (PLK_SMAP_KEEP if keep else 0)
+        self._chk(self.lib.plk_smap_sample(self.h, int(root), len(b), b.ctypes.data_as(ip), mp, _d(tt), int(seed),
+                                           int(replicate0), int(n_replicates), int(site0), flags))
+
+    def smap_sums(self, branches) -> dict:
+        """plk_smap_get_sums: "counts" [branch, pattern, type] (uint32) and "dwell" [branch, pattern,
+        state], summed over the sampled replicates."""
+        br = np.ascontiguousarray(branches, dtype=np.int32).ravel()
+        out = {"counts": np.empty((len(br), self.P, self.smap_T), dtype=np.uint32),
+               "dwell": np.empty((len(br), self.P, self.S))}
+        self._chk(self.lib.plk_smap_get_sums(self.h, len(br), br.ctypes.data_as(ct.POINTER(ct.c_int32)),
+                                             out["counts"].ctypes.data_as(ct.POINTER(ct.c_uint32)), _d(out["dwell"])))
+        return out
+
+    def smap_tallies(self, nodes) -> dict:
+        """plk_smap_get_tallies: "states" [node, pattern, state] and "classes" [pattern, class] (uint32)."""
+        nd = np.ascontiguousarray(nodes, dtype=np.int32).ravel()
+        out = {"states": np.empty((len(nd), self.P, self.S), dtype=np.uint32),
+               "classes": np.empty((self.P, self.C), dtype=np.uint32)}
+        u32 = ct.POINTER(ct.c_uint32)
+        self._chk(self.lib.plk_smap_get_tallies(self.h, len(nd), nd.ctypes.data_as(ct.POINTER(ct.c_int32)),
+                                                out["states"].ctypes.data_as(u32) if len(nd) else None,
+                                                out["classes"].ctypes.data_as(u32)))
+        return out
+
+    def smap_totals(self, branches) -> np.ndarray:
+        """plk_smap_get_totals: [branch, type], the pattern-weighted totals of the count sums."""
+        br = np.ascontiguousarray(branches, dtype=np.int32).ravel()
+        out = np.empty((len(br), self.smap_T))
+        self._chk(self.lib.plk_smap_get_totals(self.h, len(br), br.ctypes.data_as(ct.POINTER(ct.c_int32)), _d(out)))
+        return out
+
+    def smap_states(self, replicate: int, node: int) -> np.ndarray:
+        out = np.empty(self.P, dtype=np.uint8)
+        self._chk(self.lib.plk_smap_get_states(self.h, int(replicate), int(node), out.ctypes.data_as(ct.POINTER(ct.c_uint8))))
+        return out
+
+    def smap_classes(self, replicate: int) -> np.ndarray:
+        out = np.empty(self.P, dtype=np.uint8)
+        self._chk(self.lib.plk_smap_get_classes(self.h, int(replicate), out.ctypes.data_as(ct.POINTER(ct.c_uint8))))
+        return out
+
+    def smap_jumps(self, replicate: int, branch: int) -> np.ndarray:
+        out = np.empty(self.P, dtype=np.uint16)
+        self._chk(self.lib.plk_smap_get_jumps(self.h, int(replicate), int(branch), out.ctypes.data_as(ct.POINTER(ct.c_uint16))))
+        return out
+
+    def smap_counts(self, replicate: int, branch: int) -> np.ndarray:
+        out = np.empty((self.P, self.smap_T), dtype=np.uint16)
+        self._chk(self.lib.plk_smap_get_counts(self.h, int(replicate), int(branch), out.ctypes.data_as(ct.POINTER(ct.c_uint16))))
+        return out
+
+    def smap_dwell(self, replicate: int, branch: int) -> np.ndarray:
+        out = np.empty((self.P, self.S))
+        self._chk(self.lib.plk_smap_get_dwell(self.h, int(replicate), int(branch), _d(out)))
+        return out
+
+    def smap_tables(self, model: int, branch: int) -> dict:
+        """plk_smap_get_tables: "R" [S, S], "Rpow" [129, S, S] of the model, "pois" [C, 129] of the branch."""
+        N1 = PLK_SMAP_MAX_JUMPS + 1
+        out = {"R": np.empty((self.S, self.S)), "Rpow": np.empty((N1, self.S, self.S)), "pois": np.empty((self.C, N1))}
+        self._chk(self.lib.plk_smap_get_tables(self.h, int(model), _d(out["R"]), _d(out["Rpow"]), int(branch), _d(out["pois"])))
+        return out
+
+    def smap_bad(self) -> int:
+        n = ct.c_int64(0)
+        self._chk(self.lib.plk_smap_bad(self.h, ct.byref(n)))
+        return n.value
+
+    def smap_launches(self) -> int:
+        n = ct.c_int64(0)
+        self._chk(self.lib.plk_smap_launches(self.h, ct.byref(n)))
         return n.value
 
     def set_timing(self, on: bool):

@@ -736,6 +736,101 @@ int plk_sim_get_classes(plk_handle h, uint8_t* classes /* n_patterns */);
 /* Kernel launches (per shard) of the last plk_simulate on this handle. */
 int plk_sim_launches(plk_handle h, int64_t* launches);
 
+/* Stochastic mapping (csrc/plk_smap.hpp): histories of substitutions along every branch, drawn
+ * from their posterior given the tips (Nielsen 2002; the reference's Mapping/StochasticMapping.cpp
+ * samples a site at a time and a branch by rejection).  Ancestral states are drawn down the tree
+ * from the stored lower partials, then an endpoint-conditioned path per branch by uniformisation
+ * (Hobolth & Stone 2009): the number of jumps, the chain of states, the spacings.
+ *
+ * Definition.  All draws use plk_simulate's generator and uniform: u = (w >> 11) 2^-53 of word
+ * k & 3 of Philox4x64-10(counter = (site, k >> 2, replicate, c3), key = (seed, 0)); plk_simulate has
+ * c3 = 0, here c3 = 1 for the ancestral draws and c3 = 2 + v for the path on branch v (a child node
+ * index), so no draw is shared with a simulation of the same seed.  Every result is a pure function
+ * of (seed, replicate, global site = site0 + pattern, node): launch geometry, sharding and the
+ * batching of replicates into calls change nothing.
+ *   Weighted draw, the one rule used below: weights w[0..n), each formed as stated and replaced by
+ *     0 unless it is > 0; cum the sequential fp64 sum; thr = u * cum[n-1] (one rounded multiply); the
+ *     result is the first y with thr < cum[y], else the largest y with w[y] > 0 (0 if there is none).
+ *     A weight that is a product p * q is rounded before it enters a sum (no fused multiply-add).
+ *   Ancestral states (c3 = 1; k = 0 the class, 1 the root, 2 + v node v), with L the stored lower
+ *     partial (a tip: its code's row of the code table) and P the device P(t):
+ *       class  w_c = p_c * (sum_x pi_x * L_root[c][x]), the inner sum sequential in x;
+ *       root   w_x = pi_x * L_root[c][x];
+ *       node v with father state f: w_y = P_v[c][f][y] * L_v[c][y], tips included (an ambiguous or
+ *       gap tip gets a sampled state, a resolved tip its own).
+ *     Under PLK_FLAG_SCALING a stored vector carries one power of two over all classes and states,
+ *     which multiplies thr and cum alike: nothing is unscaled.  A site whose class total is not a
+ *     positive finite number is bad: its states and class are 255, its counts and dwelling times 0,
+ *     the sums skip it, and each of its replicates is counted in n_bad (no error, as the posteriors).
+ *   Tables, built on the device.  Q_m is the generator of plk_smap_set_generator; mu_m =
+ *     max_x(-Q_m[x][x]); R_m = I + Q_m / mu_m; Rpow_m[0] = I, Rpow_m[n] = Rpow_m[n-1] R_m for
+ *     n <= PLK_SMAP_MAX_JUMPS; per branch and class lambda = mu_m r_c t_v, pois[v][c][0] =
+ *     exp(-lambda), pois[n] = pois[n-1] lambda / n.  lambda > 32 is PLK_ERR_UNSUPPORTED (below it the
+ *     Poisson tail beyond 128 is under 1e-30).  plk_smap_get_tables reads them back.
+ *   Path on branch v from a = the father's state to b = v's state in class c (c3 = 2 + v):
+ *     number of jumps (k = 0): the weighted draw over n = 0..128 of w_n = pois[v][c][n] *
+ *       Rpow[n][a][b] with thr = u * P_v[c][a][b] in the place of u * cum[128] (the two agree to
+ *       rounding, and a scan can stop at the first hit); the fallback is the largest n with w_n > 0;
+ *       with no w_n > 0 at all n = 0 where a = b, else n = 1 (the direct jump, counted in n_bad);
+ *     states (k = 2i - 1, i = 1..n-1): x_0 = a, x_n = b, x_i the weighted draw of w_y =
+ *       R[x_{i-1}][y] * Rpow[n-i][y][b];
+ *     spacings (k = 2i + 2, i = 0..n): e_i = -log(1 - u); segment i lasts (t_v * e_i) / sum_i e_i
+ *       (the sum sequential in i) in state x_i.  n = 0: no draw, the whole of t_v in state a.
+ *     A jump with x_i = x_{i-1} is virtual and no event; a real one x -> y has the type
+ *     type_of[x][y] of plk_smap_set_types (0: not counted, k: type k - 1 of the outputs).
+ *   Per (replicate, site, branch): n_jumps (virtual ones included), counts[T], dwell[S] (summing to
+ *   t_v); per (replicate, site): the class and the state of every node.
+ *
+ * plk_smap_sample draws replicates replicate0 .. replicate0 + n_replicates - 1 on the tree of the
+ * last plk_update_partials, whose root must be `root`; (branch, model, t) as for
+ * plk_update_count_matrices (model NULL: model 0) must list every non-root node of that tree once,
+ * t the length its P(t) was formed for.  Sums over replicates always stay on the device:
+ * count_sum[branch][pattern][T] (uint32), dwell_sum[branch][pattern][S] (double, a replicate's dwell
+ * added per site in increasing replicate order), state_tally[node][pattern][S] and
+ * class_tally[pattern][C] (uint32), the weighted totals over patterns of the count sums (workgroup
+ * sums per block of plk_block_size() patterns added in global block order: plk_branch_counts' rule)
+ * and n_bad.  PLK_SMAP_ACCUMULATE adds to the sums of the earlier calls, without it they start at 0.
+ * PLK_SMAP_KEEP also keeps this call's per-replicate rows for the plk_smap_get_* getters that take
+ * a replicate (its absolute number); PLK_ERR_OOM when they do not fit.
+ *
+ * PLK_ERR_STATE before a traversal, without P(t) of a listed branch, rates, root frequencies, a
+ * generator of a listed model or types; PLK_ERR_UNSUPPORTED on a handle with PLK_FLAG_LNL_ONLY or
+ * PLK_FLAG_SUBTREE_PATTERNS; PLK_ERR_ARG for a list that misses a branch of the tree, names one
+ * twice or names a node outside it, for n_replicates <= 0, and from a getter for a replicate that
+ * is not kept.  PLK_FLAG_DOUBLE_RECURSIVE is not needed (no upper vectors are read).
+ *
+ * At most three launches per call (tables, sampling, totals: plk_smap_launches).  A multi-device
+ * handle fans the call out with each shard's site0 advanced by its first pattern, outputs bitwise
+ * those of one device; one process per GPU passes its rank's first site and needs no collective. */
+#define PLK_SMAP_MAX_JUMPS 128
+enum { PLK_SMAP_ACCUMULATE = 1u, PLK_SMAP_KEEP = 2u };
+/* Off-diagonal entries below 0, or a generator without a positive rate, are PLK_ERR_ARG. */
+int plk_smap_set_generator(plk_handle h, int model, const double* Q /* S x S */);
+int plk_smap_set_types(plk_handle h, int n_types /* 1..16 */, const uint8_t* type_of /* S x S, entries 0..n_types */);
+int plk_smap_sample(plk_handle h, int root, int n, const int32_t* branch, const int32_t* model, const double* t,
+                    uint64_t seed, uint64_t replicate0, int n_replicates, int64_t site0, unsigned flags);
+/* Sums of the sampled replicates; either output may be NULL. */
+int plk_smap_get_sums(plk_handle h, int n_branches, const int32_t* branches,
+                      uint32_t* count_sum /* [branch][pattern][T] */, double* dwell_sum /* [branch][pattern][S] */);
+int plk_smap_get_tallies(plk_handle h, int n_nodes, const int32_t* nodes, uint32_t* state_tally /* [node][pattern][S] */,
+                         uint32_t* class_tally /* [pattern][C] */);
+int plk_smap_get_totals(plk_handle h, int n_branches, const int32_t* branches, double* totals /* [branch][T] */);
+/* Kept rows of one replicate (PLK_SMAP_KEEP). */
+int plk_smap_get_states(plk_handle h, uint64_t replicate, int node, uint8_t* states /* n_patterns */);
+int plk_smap_get_classes(plk_handle h, uint64_t replicate, uint8_t* classes /* n_patterns */);
+int plk_smap_get_jumps(plk_handle h, uint64_t replicate, int branch, uint16_t* n_jumps /* n_patterns */);
+int plk_smap_get_counts(plk_handle h, uint64_t replicate, int branch, uint16_t* counts /* [pattern][T] */);
+int plk_smap_get_dwell(plk_handle h, uint64_t replicate, int branch, double* dwell /* [pattern][S] */);
+/* The tables of the last plk_smap_sample (any output may be NULL): R and Rpow of `model`, the
+ * Poisson terms of `branch`. */
+int plk_smap_get_tables(plk_handle h, int model, double* R /* S x S */,
+                        double* Rpow /* [PLK_SMAP_MAX_JUMPS + 1][S][S] */, int branch,
+                        double* pois /* [C][PLK_SMAP_MAX_JUMPS + 1] */);
+/* Bad samples behind the current sums: replicates of bad sites plus forced direct jumps. */
+int plk_smap_bad(plk_handle h, int64_t* n_bad);
+/* Kernel launches (per shard) of the last plk_smap_sample on this handle. */
+int plk_smap_launches(plk_handle h, int64_t* launches);
+
 /* Instrumentation: HIP-event timing on the handle's stream of the kernels selected
  * by the mask given to plk_set_timing (0 = off).  Each timed launch adds an event
  * pair to the stream, so time only what is needed. */
