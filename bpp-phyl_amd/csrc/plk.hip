@@ -365,6 +365,16 @@ struct plk_handle_s {
   size_t ucodes_cap = 0, units_cap = 0;
   bool ucodes_valid = false;    // cleared by new tip codes and by a new plan
   int jit_resident = 0;  // workgroups of jit_fn resident at once on the device
+  // table image of a JitShape::img kernel (plk_jit.hpp jit_tabs4_source): the tables of every
+  // fragment and class in the traversal's LDS layout, [fragment][class][TD] doubles, built by the
+  // module's builder kernel -- with the P(t) request (plk_update_pmatrices), or from pmats / tipP
+  // as stored when the image does not match them (update_tree4)
+  double* d_tab_img = nullptr;
+  size_t tab_img_cap = 0;
+  bool tab_img_valid = false;           // the image matches pmats, tipP and the plan
+  hipFunction_t jit_tabs_fn[2] = {nullptr, nullptr};  // the builder of jit_fn's module: small / full argument block
+  int tab_units = 0;                    // table units of the plan, all fragments (builder blocks per class)
+  std::vector<int> tab_branches;        // the branches those units read
   std::string kernel_path;                // what served the last plk_update_partials
   // per-subtree pattern compression (PLK_FLAG_SUBTREE_PATTERNS)
   std::vector<std::vector<uint8_t> > tip_codes_host;  // compact codes per tip
@@ -673,7 +683,8 @@ int collect_events(plk_handle h) {
 // stored source equals the generated one.  Modules stay loaded for the life of the process.
 // ---------------------------------------------------------------------------
 std::mutex g_jit_mutex;
-std::map<std::pair<int, std::string>, hipFunction_t> g_jit_cache;
+std::map<std::pair<int, std::string>, hipFunction_t> g_jit_cache;  // by (device, name + '\n' + source)
+std::map<std::pair<int, std::string>, hipModule_t> g_jit_modules;  // by (device, source)
 std::map<std::string, std::vector<char> > g_jit_code;  // compiled code objects by source
 
 std::string jit_cache_dir() {
@@ -799,10 +810,19 @@ int jit_compile(plk_handle h, const std::string& src, std::vector<char>* code, b
 
 int jit_function(plk_handle h, const std::string& src, const char* name, hipFunction_t* out) {
   std::lock_guard<std::mutex> lock(g_jit_mutex);
-  const auto key = std::make_pair(h->device, src);
+  const auto key = std::make_pair(h->device, std::string(name) + "\n" + src);
   auto it = g_jit_cache.find(key);
   if (it != g_jit_cache.end()) {
     *out = it->second;
+    return PLK_OK;
+  }
+  // (a second kernel of a loaded module: the table image builder next to its traversal)
+  auto mt = g_jit_modules.find(std::make_pair(h->device, src));
+  if (mt != g_jit_modules.end()) {
+    hipFunction_t fn;
+    HIPCHK(h, hipModuleGetFunction(&fn, mt->second, name));
+    g_jit_cache.emplace(key, fn);
+    *out = fn;
     return PLK_OK;
   }
   auto ct = g_jit_code.find(src);
@@ -842,6 +862,7 @@ int jit_function(plk_handle h, const std::string& src, const char* name, hipFunc
     if (int rc = jit_compile(h, src, &code, true, &from_cache)) return rc;
     if (!load()) return fail(h, PLK_ERR_DEVICE, "hipModuleLoadData of the recompiled tree kernel failed");
   }
+  g_jit_modules.emplace(std::make_pair(h->device, src), mod);
   hipFunction_t fn;
   HIPCHK(h, hipModuleGetFunction(&fn, mod, name));
   g_jit_cache.emplace(key, fn);
@@ -957,6 +978,7 @@ int refresh_tip_tables(plk_handle h) {
     HIPCHK(h, hipGetLastError());
   }
   std::fill(h->tip_table_valid.begin(), h->tip_table_valid.end(), 1);
+  h->tab_img_valid = false;  // tipP changed
   return PLK_OK;
 }
 
@@ -974,6 +996,7 @@ int upload_compact_table(plk_handle h) {
   HIPCHK(h, hipMemcpy(h->code_table, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice));
   h->n_codes = U;
   h->tip_table_valid.assign(h->n_tips, 0);
+  h->tab_img_valid = false;
   return PLK_OK;
 }
 
@@ -1025,6 +1048,8 @@ int root_finish_c(plk_handle h, double* lnl, double* block_sums);
 namespace {
 double* block_target(plk_handle h);
 int launch_cls_blocks(plk_handle h, int guard, int32_t* uflow, bool site);
+bool tab_image_serves(plk_handle h, unsigned deriv_mask, bool tips_fused);
+int launch_tab_image(plk_handle h, const PmatArgs& a, const PmatInline& inl);
 
 // The root reductions of an unscaled handle flag a site likelihood below 2^-255 (or <= 0, or
 // NaN) in mapped host memory (plk_root_underflow); a scaled handle's reductions see rescaled
@@ -1297,7 +1322,7 @@ int plk_destroy(plk_handle h) {
                   h->count_G, h->wmats, h->d_mapb, h->map_blk, h->d_mapreq, h->d_nni, h->nni_vit, h->d_pair,
                   h->rell_rows, h->rell_W, h->rell_stage, h->rell_bad, h->pars_sets, h->pars_scores, h->d_pars,
                   h->d_pars_moves, h->sim_states, h->d_sim, h->d_smap_tab, h->d_smap_pois, h->d_smap_list,
-                  h->d_smap_sums, h->d_smap_work, h->d_smap_keep};
+                  h->d_smap_sums, h->d_smap_work, h->d_smap_keep, h->d_tab_img};
   for (void* p : bufs)
     if (p) hipFree(p);
   if (h->h_req) (void)hipHostFree(h->h_req);
@@ -1641,6 +1666,7 @@ int plk_update_pmatrices(plk_handle h, int n, const int32_t* branch, const int32
   a.n_tips = h->n_tips;
   a.n_codes = h->n_codes;
   TimedSpan span(h, PLK_TIME_PMAT, 1);
+  bool built_image = false;
   const size_t lds = (size_t)(h->S + (tips_fused ? 3 : 2) * S2) * sizeof(double);
   // pmat64s_kernel and pmat_kernel also write the transposed copy the matrix-core kernels
   // read (allocated by the first transposed-P use), so an evaluation needs no transpose launch
@@ -1661,6 +1687,11 @@ int plk_update_pmatrices(plk_handle h, int n, const int32_t* branch, const int32
       PLK_P64W(4, 1) PLK_P64W(4, 2) PLK_P64W(4, 4)
 #undef PLK_P64W
     }
+  } else if (h->S == 4 && tab_image_serves(h, deriv_mask, tips_fused)) {
+    // a current one-class-per-workgroup plan with a table image: its builder kernel does this
+    // request's rows and builds the traversal's tables in the same launch (plk_jit.hpp)
+    built_image = true;
+    if (int rc = launch_tab_image(h, a, inl)) return rc;
   } else if (h->S == 4)
   {
     const dim3 g4((unsigned)((n * h->C * 4 + 63) / 64));
@@ -1703,6 +1734,14 @@ int plk_update_pmatrices(plk_handle h, int n, const int32_t* branch, const int32
       if (branch[i] < h->n_tips) h->tip_table_valid[branch[i]] = tips_fused ? 1 : 0;  // row written by pmat_kernel
     }
   }
+  // The table image matches when its builder saw every branch of its units: in this request, or
+  // valid in pmats / tipP.  P(t) written by any other kernel leaves it behind.
+  h->tab_img_valid = false;
+  if (built_image) {
+    h->tab_img_valid = true;
+    for (int b : h->tab_branches)
+      if (!h->pmat_valid[b] || (b < h->n_tips && !h->tip_table_valid[b])) h->tab_img_valid = false;
+  }
   if (h->deriv_valid.empty()) h->deriv_valid.assign(h->n_nodes, 0);
   // dP/d2P stay consistent with P only when all three come from the same call
   const bool both = (deriv_mask & (PLK_DERIV_P | PLK_DERIV_DP | PLK_DERIV_D2P)) ==
@@ -1724,6 +1763,7 @@ int plk_set_pmatrix(plk_handle h, int branch, const double* P) {
   h->pmatsT_dirty = true;
   if (!h->deriv_valid.empty()) h->deriv_valid[branch] = 0;
   if (branch < h->n_tips) h->tip_table_valid[branch] = 0;
+  h->tab_img_valid = false;  // P(t) changed behind the table image
   return PLK_OK;
 }
 
@@ -2114,6 +2154,7 @@ int build_tree4_program(plk_handle h, const plk_op* ops, int n_ops, bool materia
   h->prog_host = prog;
   h->frag_starts_host.assign(start_sorted.begin(), start_sorted.begin() + nf);
   h->jit_fn = nullptr;  // specialised kernel of the new program: compiled on first use
+  h->tab_img_valid = false;
   h->jitm_fn = nullptr;
   h->jit_plan_valid = false;
   HIPCHK(h, hipStreamSynchronize(h->stream));  // host staging vectors go out of scope
@@ -2311,6 +2352,7 @@ void jit4_ensure_plan(plk_handle h, int U, bool scale) {
   h->jit_plan_budget = budget;
   h->jit_plan_qb = qb;
   h->jit_fn = nullptr;
+  h->tab_img_valid = false;
   h->ucodes_valid = false;
 }
 
@@ -2371,6 +2413,10 @@ int jit4_shape(plk_handle h, JitShape& sh) {
   // every workgroup owns floor or ceil of n_tasks / gridDim.x tasks and a wave that ran slowly
   // takes fewer of them (plk_jit.hpp)
   sh.wp = sh.wt && tune_int("JIT_WP", sh.cls ? 1 : 0, 0, 1) != 0;
+  // table image (one class per workgroup; PLK_TUNE JIT_IMG=0 keeps the build in every traversal
+  // workgroup's prologue, for A/B runs): the tables are built once per class next to the P(t)
+  // request and a workgroup's prologue is one copy (plk_jit.hpp)
+  sh.img = sh.cls && tune_int("JIT_IMG", 1, 0, 1) != 0;
   // two patterns per lane halve the P(t) reads per FMA but double the registers:
   // measured slower (cfg2 0.255-0.301 vs 0.241 ms), so opt-in; not with speculation
   // two-stage pipeline, codes / HBM loads 3 ahead (cfg2 0.274 -> 0.259 ms); with every
@@ -2442,10 +2488,97 @@ int jit4_unit_codes(plk_handle h, const JitShape& sh) {
 // Compile the generated tree4 kernel when there is none for this plan and shape
 int jit4_compile(plk_handle h, const JitShape& sh) {
   if (h->jit_fn && sh == h->jit_shape) return PLK_OK;
-  int rc = jit_function(h, jit_tree4_source(h->jit_plan, sh), jit_tree4_name(sh), &h->jit_fn);
+  h->tab_img_valid = false;
+  h->jit_tabs_fn[0] = h->jit_tabs_fn[1] = nullptr;
+  const std::string src = jit_tree4_source(h->jit_plan, sh);
+  int rc = jit_function(h, src, jit_tree4_name(sh), &h->jit_fn);
   if (rc) return rc;
+  if (sh.img) {
+    // the builder kernels of the same module, the image and the branches its units read
+    for (int l = 0; l < 2 && !rc; ++l) rc = jit_function(h, src, jit_tabs4_name(l != 0), &h->jit_tabs_fn[l]);
+    const size_t bytes = h->jit_plan.units.size() * (size_t)h->C * std::max(sh.TD, 4) * sizeof(double);
+    const size_t cap0 = h->tab_img_cap;
+    if (!rc) rc = ensure_cap(h, (void**)&h->d_tab_img, &h->tab_img_cap, bytes);
+    // (a fragment's image past its own tables is copied but never read: zeros, not stale bytes)
+    if (!rc && h->tab_img_cap != cap0) HIPCHK(h, hipMemsetAsync(h->d_tab_img, 0, h->tab_img_cap, h->stream));
+    if (rc) {
+      h->jit_fn = nullptr;
+      return rc;
+    }
+    h->tab_units = 0;
+    h->tab_branches.clear();
+    for (const auto& un : h->jit_plan.units)
+      for (const JitUnit& u : un) {
+        ++h->tab_units;
+        for (int b : {u.ta, u.tb, u.tc, u.td, u.br, u.brA, u.brB})
+          if (b >= 0) h->tab_branches.push_back(b);
+      }
+  }
   h->jit_shape = sh;
   h->jit_resident = 0;
+  return PLK_OK;
+}
+
+// A P-only request of a 4-state handle goes through the table image builder when the handle's
+// compiled traversal is a current JitShape::img kernel for the codes in use
+bool tab_image_serves(plk_handle h, unsigned deriv_mask, bool tips_fused) {
+  return h->S == 4 && deriv_mask == PLK_DERIV_P && tips_fused && h->jit_fn && h->jit_plan_valid && h->jit_plan_cls &&
+         h->jit_shape.img && h->jit_shape.U == h->n_codes && h->jit_tabs_fn[0] && h->jit_tabs_fn[1] && h->d_tab_img &&
+         !tune_is("JIT_IMG", '0');
+}
+
+// The builder launch: ceil(n_req C 4 / 256) blocks for the request's rows (none for an empty
+// request), then one block per table unit and class
+int launch_tab_image(plk_handle h, const PmatArgs& a, const PmatInline& inl) {
+  PmatArgs pa = a;
+  double* img = h->d_tab_img;
+  int nlead = (pa.n_req * h->C * 4 + 255) / 256;
+  const unsigned grid = (unsigned)(nlead + h->tab_units * h->C);
+  if (grid == 0) return PLK_OK;
+  if (inl.n <= kPmatInlineSmall) {  // (also the empty and the staged request, n = 0)
+    PmatInlineSmall sm;
+    sm.n = inl.n;
+    std::copy(inl.t, inl.t + inl.n, sm.t);
+    std::copy(inl.branch, inl.branch + inl.n, sm.branch);
+    std::copy(inl.model, inl.model + inl.n, sm.model);
+    void* args[] = {&pa, &sm, &img, &nlead};
+    HIPCHK(h, hipModuleLaunchKernel(h->jit_tabs_fn[0], grid, 1, 1, 256, 1, 1, 0, h->stream, args, nullptr));
+  } else {
+    PmatInline full = inl;
+    void* args[] = {&pa, &full, &img, &nlead};
+    HIPCHK(h, hipModuleLaunchKernel(h->jit_tabs_fn[1], grid, 1, 1, 256, 1, 1, 0, h->stream, args, nullptr));
+  }
+  return PLK_OK;
+}
+
+// update_tree4's table image stage: an image that does not match pmats / tipP (P(t) came by
+// another route, or before the plan existed) is rebuilt from them by the same builder with an
+// empty request -- one launch more on that path only
+int jit4_table_image(plk_handle h) {
+  if (!h->jit_shape.img || h->tab_img_valid) return PLK_OK;
+  for (int b : h->tab_branches)
+    if (!h->pmat_valid[b]) return fail(h, PLK_ERR_STATE, "transition matrix of branch %d not set", b);
+  PmatArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.rates = h->rates;
+  a.V = h->V;
+  a.Vinv = h->Vinv;
+  a.lambda = h->lambda;
+  a.P = h->pmats;
+  a.init = h->code_table;
+  a.tipP = h->tipP;
+  a.n_tips = h->n_tips;
+  a.n_codes = h->n_codes;
+  a.S = h->S;
+  a.C = h->C;
+  a.mask = PLK_DERIV_P;
+  a.uni_model = -1;
+  PmatInline inl;
+  inl.n = 0;
+  TimedSpan span(h, PLK_TIME_TABLES, 3);
+  if (int rc = launch_tab_image(h, a, inl)) return rc;
+  if (span.stop()) h->n_table_launches++;
+  h->tab_img_valid = true;
   return PLK_OK;
 }
 
@@ -2464,6 +2597,7 @@ int jit4_args(plk_handle h, int32_t* uflow, JArgs& ja) {
     if (rc) return rc;
     ja.cls_sum = h->d_cls;
   }
+  ja.tab_img = h->d_tab_img;
   return PLK_OK;
 }
 
@@ -2630,6 +2764,7 @@ int update_tree4(plk_handle h, const plk_op* ops, int n_ops) {
     if (!rc) rc = jit4_unit_codes(h, sh);
     if (!rc) rc = jit4_compile(h, sh);
     if (!rc) rc = jit4_args(h, a.uflow, ja);
+    if (!rc) rc = jit4_table_image(h);
     if (rc) return rc;
   }
   const bool jitm = kind == FK_TREEM && h->prog_jitm;

@@ -434,9 +434,15 @@ struct JArgs {
   // only by the wave-task programs' prelude (kJitArgsTail / kJitArgsTailWt): the other
   // programs' JArgs ends at cls_sum and their sources stay as they were
   int32_t n_tasks;
+  // JitShape::img: the table images, [fragment][class][TD] doubles (jit_tabs4_name).  Declared
+  // only by those programs' prelude (kJitArgsTailImg, behind n_tasks)
+  const double* tab_img;
 };
 static const char* kJitArgsTail = "[C][n_pad]\n};";
 static const char* kJitArgsTailWt = "[C][n_pad]\n  i32 n_tasks;  // wave tasks (64 * PW_ patterns each)\n};";
+static const char* kJitArgsTailImg =
+    "[C][n_pad]\n  i32 n_tasks;  // wave tasks (64 * PW_ patterns each)\n"
+    "  const double* tab_img;  // table images [fragment][class][TD_], in the layout of tab\n};";
 
 struct JitShape {
   // a new field goes into tied() too: operator== decides whether a compiled kernel still fits
@@ -476,8 +482,14 @@ struct JitShape {
   // (jit_pool_task) and its waves draw them from one LDS counter, whichever wave is free next --
   // no global atomic, no barrier, no wave waiting for another
   bool wp = false;
+  // table image (cls): the fragment's tables are built once per class by the builder kernel that
+  // the module carries next to the traversal (jit_tabs4_name: blocks in front of it do the P(t)
+  // request's rows, so it stands in for pmat4_kernel's launch), and a traversal workgroup's
+  // prologue is one copy of its fragment's and class's image into LDS
+  bool img = false;
   auto tied() const {
-    return std::tie(C, CW, PW, pin, G, U, NT, TD, scale, L, RD, minw, ppipe, clk, cls, QT, soa, ps1, dc, dcw, wt, wp);
+    return std::tie(C, CW, PW, pin, G, U, NT, TD, scale, L, RD, minw, ppipe, clk, cls, QT, soa, ps1, dc, dcw, wt, wp,
+                    img);
   }
   bool operator==(const JitShape& o) const { return tied() == o.tied(); }
   int nw() const { return cls ? 1 : C / CW; }  // waves per pattern group
@@ -488,8 +500,9 @@ struct JitShape {
     // rescale) -- none with one class per workgroup
     const size_t xch = cls ? 0 : (scale ? 2 : 1) * (size_t)PW * G * nw() * 64 * sizeof(double);
     // the code rows' space also holds the quad build's cherry rows before the first super-block
+    // (none with a table image: the quads come built)
     return (size_t)std::max(TD, 4) * sizeof(double) + xch +
-           std::max(dc ? (size_t)0 : (size_t)G * nt * 64 * PW, (size_t)QT * sizeof(double));
+           std::max(dc ? (size_t)0 : (size_t)G * nt * 64 * PW, img ? (size_t)0 : (size_t)QT * sizeof(double));
   }
 };
 
@@ -504,6 +517,9 @@ inline int jit_pool_task(int x, int gx, int j) { return PLK_POOL_TASK_EXPR(x, gx
 // The generated kernel's name: one class per workgroup is plk_jit_tree4c, so that kernel-trace
 // statistics keep it apart from the classes-in-the-wave kernel (plk_jit_tree4) of other configs
 inline const char* jit_tree4_name(const JitShape& sh) { return sh.cls ? "plk_jit_tree4c" : "plk_jit_tree4"; }
+// The table image builder of a JitShape::img module: the request inline in the 1 KB argument
+// block (up to kPmatInlineSmall branches), or in the full one / the staging (large)
+inline const char* jit_tabs4_name(bool large) { return large ? "plk_jit_tabs4c_l" : "plk_jit_tabs4c"; }
 
 // Pattern groups per workgroup with the most waves resident per CU: LDS (160 KiB per CU)
 // against the tables every workgroup stages once, and VGPRs at the ~72 registers these
@@ -671,6 +687,263 @@ inline JitPlan jit_plan(const std::vector<TInstr>& prog, const std::vector<int32
   return plan;
 }
 
+// JitShape::img: the traversal's prologue.  The fragment's tables come built (the builder kernel
+// wrote this fragment's and class's image in the layout of tab), so every wave copies its share:
+// 16 bytes per access, every load of a round (eight per thread: one round for 128 KB of tables
+// and 1 024 threads) issued before the round's first LDS store.
+static const char* kJitImgCopy = R"PLKJIT(  double ptouch_ = 0.0;
+  {
+    const double2* src_ = reinterpret_cast<const double2*>(a.tab_img + ((i64)frag * C_ + c0) * TD_);
+    double2* dst_ = reinterpret_cast<double2*>(tab);
+    constexpr int NV_ = 8, NH_ = TD_ / 2, RS_ = NV_ * 64 * NWT_;
+    _Pragma("nounroll") for (int k0_ = 0; k0_ < NH_; k0_ += RS_) {
+      double2 r_[NV_];
+      _Pragma("unroll") for (int q_ = 0; q_ < NV_; ++q_) {
+        const int k_ = k0_ + (int)threadIdx.x + 64 * NWT_ * q_;
+        r_[q_] = src_[k_ < NH_ ? k_ : 0];
+      }
+      _Pragma("unroll") for (int q_ = 0; q_ < NV_; ++q_) {
+        const int k_ = k0_ + (int)threadIdx.x + 64 * NWT_ * q_;
+        if (k_ < NH_) dst_[k_] = r_[q_];
+      }
+    }
+  }
+)PLKJIT";
+
+// JitShape::img: the builder kernels (jit_tabs4_name), emitted behind the traversal so that they
+// read its constants (kQuadD, kOtherD, the layout macros).  One launch, 256 threads per block:
+//   * blocks [0, nlead): the P(t) request, one thread per (entry, class, row x) -- pmat4_kernel's
+//     row (plk_kernels.hpp) restated with its operations in its order, so pmats and tipP get the
+//     bits pmat4_kernel writes.  Inline or staged request, as there.
+//   * block nlead + k * C_ + c: table unit k (the module's quads, then its other units) of class
+//     c, written to img[fragment][c] at the unit's offset in the traversal's LDS layout.  No
+//     block waits for another: for each of the unit's branches (at most four tips, two cherries
+//     and Q) that the request names, the block computes the rows it needs with the same row
+//     function (t == 0 gives the identity as there); a branch the request does not name is read
+//     from pmats / tipP as stored.  An empty request (nlead = 0) rebuilds the image from memory.
+// The table arithmetic is the text of the traversal's former prologue, moved: the pair product,
+// pcon through the cherry's P, acc = contA, acc *= contB, pcon through P_Q -- only P(t) and the
+// tip rows come from LDS (sP_, sT_) instead of scalar and global loads.
+inline std::string jit_tabs4_source(const JitPlan& plan) {
+  std::string qf = "__device__ const int kQuadFrag[] = {0", of = "};\n__device__ const int kOtherFrag[] = {0";
+  char buf[64];
+  int nq = 0, no = 0;
+  for (size_t f = 0; f < plan.units.size(); ++f)
+    for (const JitUnit& u : plan.units[f]) {
+      snprintf(buf, sizeof(buf), ",%zu", f);
+      if (u.tc >= 0) {
+        qf += buf;
+        ++nq;
+      } else {
+        of += buf;
+        ++no;
+      }
+    }
+  std::string s = qf + of + "};\n";
+  snprintf(buf, sizeof(buf), "#define NQA_ %d\n#define NOA_ %d\n", nq, no);
+  s += buf;
+  s += R"PLKJIT(struct PmatArgs {  // (plk_kernels.hpp: the same fields in the same order)
+  const i32* branch; const i32* model; const double* t; const double* rates; const double* V; const double* Vinv;
+  const double* lambda; double* P; double* PT; double* dP; double* d2P; const double* init; double* tipP;
+  int n_tips, n_codes; int S, C; unsigned mask; int n_req; int uni_model;
+};
+template <int N> struct PmatInl { double t[N]; i32 branch[N]; i32 model[N]; i32 n; };
+// row x of P(t) for class c of a request entry (length t, model m)
+__device__ __forceinline__ void pmat4_row(const PmatArgs& a, double t, int m, int c, int x, double (&p)[4]) {
+  constexpr int S = 4;
+  const double rc = a.rates[c];
+  const double tt = t * rc;
+  const double* V = a.V + (size_t)m * S * S;
+  const double* Vi = a.Vinv + (size_t)m * S * S;
+  const double* lam = a.lambda + (size_t)m * S;
+  double e[S], l[S], vx[S], vi[S * S];
+#pragma unroll
+  for (int k = 0; k < S; ++k) {
+    l[k] = lam[k];
+    vx[k] = V[x * S + k];
+  }
+#pragma unroll
+  for (int k = 0; k < S * S; ++k) vi[k] = Vi[k];
+#pragma unroll
+  for (int k = 0; k < S; ++k) e[k] = exp(l[k] * tt);
+#pragma unroll
+  for (int y = 0; y < S; ++y) {
+    p[y] = 0.0;
+#pragma unroll
+    for (int k = 0; k < S; ++k) {
+      const double w = vx[k] * vi[k * S + y];
+      p[y] = __builtin_fma(w, e[k], p[y]);
+    }
+    if (tt == 0.0) p[y] = (x == y) ? 1.0 : 0.0;  // getPij_t: t == 0 -> identity
+  }
+}
+// entry x of a tip's table row of one code: sum_y P[x][y] init[code][y]
+__device__ __forceinline__ double tip4_entry(const PmatArgs& a, const double (&p)[4], int code) {
+  double t = 0.0;
+#pragma unroll
+  for (int y = 0; y < 4; ++y) t = __builtin_fma(p[y], a.init[code * 4 + y], t);
+  return t;
+}
+template <class Inl>
+__device__ __forceinline__ void tabs4_body(const PmatArgs& a, const Inl& inl, double* __restrict__ img, int nlead) {
+  const int tid = threadIdx.x;
+  if ((int)blockIdx.x < nlead) {
+    const int gid = blockIdx.x * 256 + tid;
+    if (gid >= a.n_req * C_ * 4) return;
+    const int x = gid & 3, ic = gid >> 2, i = ic / C_, c = ic - i * C_;
+    const int b = inl.n ? inl.branch[i] : a.branch[i];
+    const int m = inl.n ? inl.model[i] : (a.model ? a.model[i] : 0);
+    double p[4];
+    pmat4_row(a, inl.n ? inl.t[i] : a.t[i], m, c, x, p);
+    const size_t off = ((size_t)b * C_ + c) * 16 + x * 4;
+#pragma unroll
+    for (int y = 0; y < 4; ++y) a.P[off + y] = p[y];
+    if (a.init && b < a.n_tips) {
+      double* out = a.tipP + ((size_t)b * C_ + c) * (U_ * 4) + x;
+      for (int code = 0; code < U_; ++code) out[code * 4] = tip4_entry(a, p, code);
+    }
+    return;
+  }
+  __shared__ __attribute__((aligned(16))) double sT_[4][U_ * 4];  // the unit's tips' table rows of this class
+  __shared__ __attribute__((aligned(16))) double sP_[3][16];      // P(t) of its branches (cherry, or A, B, Q)
+  __shared__ __attribute__((aligned(16))) double sQ_[2 * U_ * U_ * 4];  // a quad's two cherries' contribution rows
+  __shared__ int sIdx_[8];                                        // request entry of tips 0..3, branches 0..2 (-1: none)
+  const int ub = (int)blockIdx.x - nlead, k = ub / C_, c0 = ub - k * C_;
+  int tp[4], br[3], off, frag;
+  if (k < NQA_) {
+    const QuadD q = kQuadD[1 + k];
+    tp[0] = q.ta; tp[1] = q.tb; tp[2] = q.tc; tp[3] = q.td;
+    br[0] = q.brA; br[1] = q.brB; br[2] = q.brQ;
+    off = q.off;
+    frag = kQuadFrag[1 + k];
+  } else {
+    const UnitD u = kOtherD[1 + k - NQA_];
+    tp[0] = u.ta; tp[1] = u.tb; tp[2] = -1; tp[3] = -1;
+    br[0] = u.br; br[1] = -1; br[2] = -1;
+    off = u.off;
+    frag = kOtherFrag[1 + k - NQA_];
+  }
+  double* dst = img + ((i64)frag * C_ + c0) * TD_ + off;
+  if (tid < 8) sIdx_[tid] = -1;
+  __syncthreads();
+  for (int i = tid; i < a.n_req; i += 256) {
+    const int b = inl.n ? inl.branch[i] : a.branch[i];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (b == tp[j]) sIdx_[j] = i;
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+      if (b == br[j]) sIdx_[4 + j] = i;
+  }
+  __syncthreads();
+  if (tid < 4 * U_ * 4) {  // tip j, row q = code * 4 + x
+    const int j = tid / (U_ * 4), q = tid - j * (U_ * 4);
+    const int tip = j == 0 ? tp[0] : j == 1 ? tp[1] : j == 2 ? tp[2] : tp[3];
+    if (tip >= 0) {
+      const int i = sIdx_[j];
+      double v;
+      if (i >= 0) {
+        double p[4];
+        pmat4_row(a, inl.n ? inl.t[i] : a.t[i], inl.n ? inl.model[i] : (a.model ? a.model[i] : 0), c0, q & 3, p);
+        v = tip4_entry(a, p, q >> 2);
+      } else {
+        v = a.tipP[((i64)tip * C_ + c0) * (U_ * 4) + q];
+      }
+      sT_[j][q] = v;
+    }
+  } else if (tid >= 64 && tid < 64 + 48) {  // branch j, element e = x * 4 + y
+    const int j = (tid - 64) >> 4, e = (tid - 64) & 15;
+    const int b = j == 0 ? br[0] : j == 1 ? br[1] : br[2];
+    if (b >= 0) {
+      const int i = sIdx_[4 + j];
+      double v;
+      if (i >= 0) {
+        double p[4];
+        pmat4_row(a, inl.n ? inl.t[i] : a.t[i], inl.n ? inl.model[i] : (a.model ? a.model[i] : 0), c0, e >> 2, p);
+        const int y = e & 3;
+        v = y == 0 ? p[0] : y == 1 ? p[1] : y == 2 ? p[2] : p[3];
+      } else {
+        v = a.P[((i64)b * C_ + c0) * 16 + e];
+      }
+      sP_[j][e] = v;
+    }
+  }
+  __syncthreads();
+  auto pcon = [&](const double* P, const double (&v_)[4], double (&t_)[4]) {
+    _Pragma("unroll") for (int x = 0; x < 4; ++x) {
+      t_[x] = P[4 * x] * v_[0];
+      t_[x] = __builtin_fma(P[4 * x + 1], v_[1], t_[x]);
+      t_[x] = __builtin_fma(P[4 * x + 2], v_[2], t_[x]);
+      t_[x] = __builtin_fma(P[4 * x + 3], v_[3], t_[x]);
+    }
+  };
+  if (tp[1] < 0) {  // a tip's rows
+    for (int i = tid; i < U_ * 4; i += 256) dst[TABIX(U_, i >> 2, i & 3)] = sT_[0][i];
+  } else if (tp[2] < 0) {
+    // a pair: one row (code pair ca, cb) per thread; through P of the cherry's branch where the
+    // unit holds the cherry's contribution (contrib<.., true>: the same operations in the same order)
+    for (int q = tid; q < U_ * U_; q += 256) {
+      const int ca = q / U_, cb = q - ca * U_;
+      const double2* pa = reinterpret_cast<const double2*>(&sT_[0][ca * 4]);
+      const double2* pb = reinterpret_cast<const double2*>(&sT_[1][cb * 4]);
+      const double2 a0 = pa[0], a1 = pa[1], b0 = pb[0], b1 = pb[1];
+      const double v[4] = {a0.x * b0.x, a0.y * b0.y, a1.x * b1.x, a1.y * b1.y};
+      double2* o0 = reinterpret_cast<double2*>(dst + TABIX(U_ * U_, q, 0));
+      double2* o1 = reinterpret_cast<double2*>(dst + TABIX(U_ * U_, q, 2));
+      if (br[0] < 0) {
+        *o0 = make_double2(v[0], v[1]);
+        *o1 = make_double2(v[2], v[3]);
+      } else {
+        double t[4];
+        pcon(sP_[0], v, t);
+        *o0 = make_double2(t[0], t[1]);
+        *o1 = make_double2(t[2], t[3]);
+      }
+    }
+  } else {
+    // a quad.  Phase 1: 2 U^2 threads form the two cherries' contribution rows; phase 2: one quad
+    // row per thread from them (the interpreter's order: each cherry's pair product and
+    // contrib<.., true> through the cherry's P, Q's accumulator = contA, *= contB, then
+    // contrib<.., true> through P_Q)
+    constexpr int U4_ = U_ * U_ * U_ * U_;
+    for (int hr = tid; hr < 2 * U_ * U_; hr += 256) {
+      const int which = hr / (U_ * U_), r = hr - which * (U_ * U_), ca = r / U_, cb = r - ca * U_;
+      const double2* pa = reinterpret_cast<const double2*>(&sT_[2 * which][ca * 4]);
+      const double2* pb = reinterpret_cast<const double2*>(&sT_[2 * which + 1][cb * 4]);
+      const double2 a0 = pa[0], a1 = pa[1], b0 = pb[0], b1 = pb[1];
+      const double v[4] = {a0.x * b0.x, a0.y * b0.y, a1.x * b1.x, a1.y * b1.y};
+      double o[4];
+      pcon(sP_[which], v, o);
+      double2* od = reinterpret_cast<double2*>(sQ_ + hr * 4);
+      od[0] = make_double2(o[0], o[1]);
+      od[1] = make_double2(o[2], o[3]);
+    }
+    __syncthreads();
+    for (int r = tid; r < U4_; r += 256) {
+      const int ab = r / (U_ * U_), cd = r - ab * (U_ * U_);
+      const double2* pa = reinterpret_cast<const double2*>(sQ_ + ab * 4);
+      const double2* pb = reinterpret_cast<const double2*>(sQ_ + (U_ * U_ + cd) * 4);
+      const double2 a0 = pa[0], a1 = pa[1], b0 = pb[0], b1 = pb[1];
+      double acc[4] = {a0.x, a0.y, a1.x, a1.y}, o[4];
+      acc[0] *= b0.x; acc[1] *= b0.y; acc[2] *= b1.x; acc[3] *= b1.y;
+      pcon(sP_[2], acc, o);
+      *reinterpret_cast<double2*>(dst + TABIX(U4_, QROW_(r), 0)) = make_double2(o[0], o[1]);
+      *reinterpret_cast<double2*>(dst + TABIX(U4_, QROW_(r), 2)) = make_double2(o[2], o[3]);
+    }
+  }
+}
+extern "C" __global__ __launch_bounds__(256) void plk_jit_tabs4c(PmatArgs a, const PmatInl<64> inl,
+                                                                 double* __restrict__ img, int nlead) {
+  tabs4_body(a, inl, img, nlead);
+}
+extern "C" __global__ __launch_bounds__(256) void plk_jit_tabs4c_l(PmatArgs a, const PmatInl<160> inl,
+                                                                   double* __restrict__ img, int nlead) {
+  tabs4_body(a, inl, img, nlead);
+}
+)PLKJIT";
+  return s;
+}
+
 // Emit the kernel for a fragment plan (jit_plan over build_tree4_program's words and
 // fragment start offsets in tier order; fragment id = frag_base + blockIdx.y).
 inline std::string jit_tree4_source(const JitPlan& plan, const JitShape& sh) {
@@ -680,10 +953,11 @@ inline std::string jit_tree4_source(const JitPlan& plan, const JitShape& sh) {
   s.reserve(4096 * events.size() + 16384);
   s += sh.ppipe ? "#define PPIPE_ 1\n" : "#define PPIPE_ 0\n";  // read by the prelude's contrib
   s += kJitPrelude;
-  if (sh.wt) {  // (JArgs::n_tasks: see the host mirror)
+  if (sh.img && !sh.cls) return std::string();
+  if (sh.wt || sh.img) {  // (JArgs::n_tasks, tab_img: see the host mirror)
     const size_t at = s.find(kJitArgsTail);
     if (at == std::string::npos) return std::string();
-    s.replace(at, std::string(kJitArgsTail).size(), kJitArgsTailWt);
+    s.replace(at, std::string(kJitArgsTail).size(), sh.img ? kJitArgsTailImg : kJitArgsTailWt);
   }
   char buf[400];
   const std::string minw_s = sh.minw > 0 ? ", " + std::to_string(sh.minw) : std::string();
@@ -889,7 +1163,10 @@ inline std::string jit_tree4_source(const JitPlan& plan, const JitShape& sh) {
   // (issued before the table staging below: its loads overlap it)
   fetch_dc((int)blockIdx.x * G_ + g);
 )PLKJIT";
-  s += R"PLKJIT(  // The fragment's P(t) matrices, touched with wide loads while the tables stage: the
+  if (sh.img)
+    s += kJitImgCopy;
+  else
+    s += R"PLKJIT(  // The fragment's P(t) matrices, touched with wide loads while the tables stage: the
   // traversal reads P(t) through scalar loads one contribution ahead, and their first touch
   // (the P(t) launch wrote them through another XCD's L2) made the first super-block ~12 us
   // slower on cfg5 (34 vs 22 us; steady state 19 us)
@@ -1058,7 +1335,8 @@ inline std::string jit_tree4_source(const JitPlan& plan, const JitShape& sh) {
       }
     }
   }
-  const CPd pm = (CPd)(pmats + c0 * 16);
+)PLKJIT";
+  s += R"PLKJIT(  const CPd pm = (CPd)(pmats + c0 * 16);
   const double* trow = tab + (CLS_ ? 0 : c0 * (U_ * 4));         // single-tip units
   const double* trow2 = tab + (CLS_ ? 0 : c0 * (U_ * U_ * 4));   // pair units
   const double* trow4 = tab;                                      // quad units (CLS_ only)
@@ -1482,6 +1760,7 @@ inline std::string jit_tree4_source(const JitPlan& plan, const JitShape& sh) {
   }
 }
 )PLKJIT";
+  if (sh.img) s += jit_tabs4_source(plan);
   if (sh.clk == 2) {
     // PLK_DEBUG_CLOCK=2: the end stamp is taken where the super-block loop starts (the prologue:
     // code fetch, table staging, quad build), not at the kernel's end.  (Inserted into the

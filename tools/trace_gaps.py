@@ -11,22 +11,24 @@ rows.sort(key=lambda r: int(r["Start_Timestamp"]))
 
 
 def short(n):
-    for k in ("pmat4", "plk_jit_tree4", "cls_blocks", "wave_sums_to_blocks", "unit_codes"):
+    # (the table image builder stands where pmat4_kernel stood: it starts an evaluation too)
+    for k in ("pmat4", "plk_jit_tabs4c", "plk_jit_tree4", "cls_blocks", "wave_sums_to_blocks", "unit_codes"):
         if k in n:
             return k
     return n[:30]
 
 
+FIRST = ("pmat4", "plk_jit_tabs4c")
 evals, cur = [], []
 for r in rows:
     k = short(r["Kernel_Name"])
-    if k == "pmat4" and cur:
+    if k in FIRST and cur:
         evals.append(cur)
         cur = []
     cur.append((k, int(r["Start_Timestamp"]), int(r["End_Timestamp"])))
 if cur:
     evals.append(cur)
-evals = [e for e in evals if e[0][0] == "pmat4"][2:]  # (skip the first evaluations)
+evals = [e for e in evals if e[0][0] in FIRST][2:]  # (skip the first evaluations)
 keys = {}
 for e in evals:
     prev_end = e[0][1]
